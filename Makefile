@@ -18,8 +18,8 @@ test-e2e: build  ## in-process e2e (emulator + promlib + controller, ~60 s)
 test-gpu: build  ## GPU tiers (run on an MI355X box)
 	$(PYTHON) -m pytest tests/ -q -m gpu
 
-bench: build  ## headline benchmark (solver wall-clock + SLO attainment)
-	$(PYTHON) bench.py --steps 20 --warmup 5
+bench: build  ## headline benchmark (solver wall-clock + SLO attainment + observed SLO)
+	$(PYTHON) bench.py --steps 20 --warmup 5 --full
 
 bench-suite: build  ## all five BASELINE configs
 	$(PYTHON) tools/bench_suite.py

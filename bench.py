@@ -25,7 +25,15 @@ per-step wall-clock is the max over ranks after a barrier, i.e. the time
 for the WHOLE fleet's global solve.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 (launched by torchrun for N>1; reads RANK/WORLD_SIZE/MASTER_* from env).
+
+A plain run does only what the headline needs: warm up, time the K
+capacity-constrained steps, print the result line.  ``--full`` adds the
+secondary measurements (the unlimited-solve series and the closed-loop
+observed-SLO run) to the same line.  ``--dump-outputs DIR`` writes what
+the last timed step computed (``solution.npy``, ``sizing.npy``; see
+``dump_outputs``) so two builds can be compared output for output.
 """
 
 from __future__ import annotations
@@ -197,9 +205,11 @@ def build_system_spec(
 
 
 def one_cycle(
-    rank: int, step: int, n_variants: int, device, limited: bool = True
+    rank: int, step: int, n_variants: int, device, limited: bool = True,
+    keep_system: bool = False,
 ) -> dict:
-    """One full optimization cycle; returns solution stats."""
+    """One full optimization cycle; returns solution stats (plus the solved
+    System under "system" when ``keep_system``)."""
     from wva_amd.ops import BatchedAllocationSolver
 
     spec = build_system_spec(rank, step, n_variants, limited=limited)
@@ -225,7 +235,51 @@ def one_cycle(
             and not server.saturated()
         ):
             met += 1
-    return {"solved": len(solution.spec), "slo_met": met, "total": total}
+    stats = {"solved": len(solution.spec), "slo_met": met, "total": total}
+    if keep_system:
+        stats["system"] = system
+    return stats
+
+
+# columns of the dumped arrays (accelerator = index into ACCELERATORS)
+SOLUTION_COLUMNS = ("accelerator", "num_replicas", "max_batch", "cost",
+                    "itl_average", "ttft_average")
+SIZING_COLUMNS = ("num_replicas", "batch_size", "cost", "itl", "ttft", "rho",
+                  "max_arrv_rate_per_replica")
+
+
+def dump_outputs(system: System, out_dir: str, suffix: str = "") -> None:
+    """Write what one cycle computed as float64 ``.npy`` files.
+
+    - ``solution.npy`` [variants, len(SOLUTION_COLUMNS)]: the exported
+      allocation solution, one row per variant in spec order; a variant
+      left unallocated is accelerator -1 and zeros.
+    - ``sizing.npy`` [variants, accelerators, len(SIZING_COLUMNS)]: the
+      batched sizing result for every (variant, accelerator) pair; an
+      infeasible pair is a row of zeros.
+    """
+    os.makedirs(out_dir, exist_ok=True)
+    acc_index = {a: i for i, a in enumerate(ACCELERATORS)}
+    solved = system.allocation_solution.spec
+    n = len(system.servers)
+    solution = np.zeros((n, len(SOLUTION_COLUMNS)), dtype=np.float64)
+    sizing = np.zeros((n, len(ACCELERATORS), len(SIZING_COLUMNS)), dtype=np.float64)
+    for i, (name, server) in enumerate(system.servers.items()):
+        data = solved.get(name)
+        if data is None:
+            solution[i, 0] = -1.0
+        else:
+            solution[i] = (
+                acc_index[data.accelerator], data.num_replicas, data.max_batch,
+                data.cost, data.itl_average, data.ttft_average,
+            )
+        for acc, alloc in server.all_allocations.items():
+            sizing[i, acc_index[acc]] = (
+                alloc.num_replicas, alloc.batch_size, alloc.cost, alloc.itl,
+                alloc.ttft, alloc.rho, alloc.max_arrv_rate_per_replica,
+            )
+    np.save(os.path.join(out_dir, f"solution{suffix}.npy"), solution)
+    np.save(os.path.join(out_dir, f"sizing{suffix}.npy"), sizing)
 
 
 def main() -> None:
@@ -236,8 +290,15 @@ def main() -> None:
     ap.add_argument("--variants-per-gpu", type=int, default=VARIANTS_PER_GPU)
     ap.add_argument("--backend", default="", help="override torch.distributed backend (default: nccl on GPU, gloo on CPU)")
     ap.add_argument("--no-observed-slo", action="store_true",
-                    help="skip the untimed closed-loop observed-SLO measurement")
+                    help="with --full: skip the untimed closed-loop observed-SLO measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: the unlimited-solve "
+                    "series and the closed-loop observed-SLO run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -270,26 +331,39 @@ def main() -> None:
     # warmup (untimed)
     for step in range(args.warmup):
         one_cycle(rank, step, n_variants, device, limited=True)
-        one_cycle(rank, step, n_variants, device, limited=False)
+        if args.full:
+            one_cycle(rank, step, n_variants, device, limited=False)
 
     # headline: capacity-constrained greedy solve
     barrier_sync()
     t0 = time.perf_counter()
     stats = []
+    # only the last step's System is kept (and only for --dump-outputs),
+    # so every other step frees its objects exactly as an undumped run
+    keep_at = args.steps - 1 if args.dump_outputs else -1
     for step in range(args.steps):
         stats.append(
-            one_cycle(rank, args.warmup + step, n_variants, device, limited=True)
+            one_cycle(rank, args.warmup + step, n_variants, device, limited=True,
+                      keep_system=step == keep_at)
         )
     barrier_sync()
     elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs:
+        dump_outputs(
+            stats[-1].pop("system"), args.dump_outputs,
+            suffix=f".rank{rank}" if world_size > 1 else "",
+        )
+
     # secondary series: the unlimited argmin solve on the same cycles
-    barrier_sync()
-    t0u = time.perf_counter()
-    for step in range(args.steps):
-        one_cycle(rank, args.warmup + step, n_variants, device, limited=False)
-    barrier_sync()
-    elapsed_unlimited = time.perf_counter() - t0u
+    elapsed_unlimited = 0.0
+    if args.full:
+        barrier_sync()
+        t0u = time.perf_counter()
+        for step in range(args.steps):
+            one_cycle(rank, args.warmup + step, n_variants, device, limited=False)
+        barrier_sync()
+        elapsed_unlimited = time.perf_counter() - t0u
 
     # max over ranks (collectives need device tensors under RCCL)
     if dist is not None:
@@ -311,7 +385,9 @@ def main() -> None:
         slo_total = float(sum(s["total"] for s in stats))
 
     ms_per_step = elapsed / args.steps * 1000.0
-    unlimited_ms_per_step = elapsed_unlimited / args.steps * 1000.0
+    secondary = {}
+    if args.full:
+        secondary["unlimited_ms_per_step"] = elapsed_unlimited / args.steps * 1000.0
     slo_attainment = 100.0 * slo_met / slo_total if slo_total else 0.0
 
     # Observed SLO attainment (untimed, single-rank runs only): a short
@@ -320,7 +396,7 @@ def main() -> None:
     # attainment measured from serving latency, not from the sizing
     # model's own predictions).
     observed = {}
-    if rank == 0 and world_size == 1 and not args.no_observed_slo:
+    if args.full and rank == 0 and world_size == 1 and not args.no_observed_slo:
         sys.path.insert(0, str(Path(__file__).resolve().parent / "tools"))
         sys.path.insert(0, str(Path(__file__).resolve().parent / "tests"))
         try:
@@ -357,7 +433,7 @@ def main() -> None:
                     "dtype": "fp64",
                     "data": "synthetic",
                     "slo_attainment_pct": slo_attainment,
-                    "unlimited_ms_per_step": unlimited_ms_per_step,
+                    **secondary,
                     **observed,
                     "config": {
                         "model": "3 models x 2 service classes (config #3)",

@@ -35,7 +35,7 @@ class TestBench:
     def test_single_process(self):
         proc = subprocess.run(
             [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
-             "--variants-per-gpu", "8", "--no-observed-slo"],
+             "--variants-per-gpu", "8", "--full", "--no-observed-slo"],
             cwd=ROOT,
             capture_output=True,
             text=True,
@@ -48,6 +48,46 @@ class TestBench:
         # easier unlimited argmin rides along as a secondary series
         assert out["unlimited_ms_per_step"] > 0
         assert "greedy-limited" in out["config"]["solver_mode"]
+
+    def test_plain_run_is_lean_and_dumps_outputs(self, tmp_path):
+        """A plain run reports only the headline, and --dump-outputs
+        writes the last timed step's arrays, identical from run to run."""
+        import numpy as np
+
+        dumps = []
+        for name in ("a", "b"):
+            proc = subprocess.run(
+                [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
+                 "--variants-per-gpu", "8", "--dump-outputs", str(tmp_path / name)],
+                cwd=ROOT,
+                capture_output=True,
+                text=True,
+                timeout=300,
+            )
+            assert proc.returncode == 0, proc.stderr
+            out = last_json_line(proc.stdout)
+            check_contract(out, n_gpus=1)
+            assert out["steps"] == 2
+            assert out["dtype"] == "fp64"
+            assert "unlimited_ms_per_step" not in out
+            assert "observed_slo_attainment_pct" not in out
+            files = sorted(p.name for p in (tmp_path / name).iterdir())
+            assert files == ["sizing.npy", "solution.npy"]
+            dumps.append({f: np.load(tmp_path / name / f) for f in files})
+
+        solution, sizing = dumps[0]["solution.npy"], dumps[0]["sizing.npy"]
+        assert solution.dtype == np.float64 and solution.shape == (8, 6)
+        assert sizing.dtype == np.float64 and sizing.shape == (8, 3, 7)
+        assert np.isfinite(solution).all() and np.isfinite(sizing).all()
+        # every allocated variant's row repeats its sizing entry
+        allocated = solution[:, 0] >= 0
+        assert allocated.any()
+        for i in np.flatnonzero(allocated):
+            acc = int(solution[i, 0])
+            assert solution[i, 1] >= 1
+            assert sizing[i, acc, 1] == solution[i, 2]  # batch size
+        for f in dumps[0]:
+            np.testing.assert_array_equal(dumps[0][f], dumps[1][f])
 
     def test_two_rank_gloo(self):
         env = dict(os.environ, MASTER_ADDR="127.0.0.1")
