@@ -151,10 +151,11 @@ class TestGPU:
         ref = _solve_problems_python(problems)
         assert_results_close(gpu, ref, rtol=1e-4)
 
-    @pytest.mark.parametrize("threads", ["64", "128", "256"])
+    @pytest.mark.parametrize("threads", ["64", "128", "256", "384", "896"])
     def test_each_geometry_matches_cpu(self, threads, monkeypatch):
         # pin each kernel geometry explicitly (the launcher's auto pick
-        # would otherwise leave two of the three unexercised)
+        # would otherwise leave most of them unexercised; N < 256 here,
+        # so the 896-thread kernel fits its LDS and is not swapped out)
         monkeypatch.setenv("WVA_GPU_THREADS", threads)
         problems = random_problems(128, seed=19)
         gpu = solve_problems(problems, device="cuda")
@@ -299,6 +300,7 @@ class TestTorchFreeCPUBinding:
             "assert ops.native_cpu_available()\n"
             "from unittest import mock\n"
             "p = np.zeros((2, ops.batched.PROBLEM_FIELDS)); p[:, 5] = 4; p[:, 6] = 2\n"
+            "p[:, 0] = 5.0; p[:, 1] = 0.05  # decode 5 ms + 0.05 ms per batch unit\n"
             "p[:, 8] = 50.0; p[:, 10] = 1.0; p[:, 11] = 1\n"
             "with mock.patch.object(ops.batched, '_solve_problems_python',\n"
             "                       side_effect=AssertionError('python fallback used')):\n"

@@ -113,8 +113,11 @@ inline void solve_one(const double *pr, double *out, double *cum) {
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
   if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  // no replicas, or a per-replica rate that is not > 0 (zero or negative
+  // load; NaN from 0/0 fails every ordered compare): infeasible
+  if (!(n_rep > 0.0)) return;
   const double rate = total_rate / n_rep;  // req/s per replica
-  if (rate <= 0.0 || rate > lam_max * 1000.0) return;
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
 
   Stats fin = eval_model(p, cum, K, rate / 1000.0);
   double rho = fin.n_serv / (double)p.max_batch;

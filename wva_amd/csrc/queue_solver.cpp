@@ -24,8 +24,10 @@
 #include "queue_host.h"
 
 #ifdef WVA_WITH_HIP
-extern "C" void wva_launch_solve(const double *prob, double *out, int n_problems,
-                                 int max_k, void *stream);
+// 0 = launched; -1 = no kernel geometry fits max_k in LDS (nothing was
+// launched); otherwise the hipError_t of the failed launch
+extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
+                                int max_k, void *stream);
 #endif
 
 static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hint = -1) {
@@ -49,12 +51,16 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
       const double max_batch = problems.select(1, wva::P_MAX_BATCH).max().item<double>();
       max_k = (int)max_batch * (1 + wva::kMaxQueueToBatchRatio);
     }
-    TORCH_CHECK((max_k + 288) * 8 <= 64 * 1024,
-                "max_batch too large for the LDS-resident GPU path (limit ~700); "
-                "use the CPU path for these problems");
     auto stream = c10::hip::getCurrentHIPStream();
-    wva_launch_solve(problems.data_ptr<double>(), out.data_ptr<double>(), (int)B,
-                     max_k, (void *)stream.stream());
+    // the launcher picks the geometry and sizes its LDS before launching
+    const int status = wva_launch_solve(problems.data_ptr<double>(),
+                                        out.data_ptr<double>(), (int)B, max_k,
+                                        (void *)stream.stream());
+    TORCH_CHECK(status != -1,
+                "max_batch too large for the LDS-resident GPU path (limit ~700, "
+                "chain length ", max_k, "); use the CPU path for these problems");
+    TORCH_CHECK(status == 0, "wva sizing kernel launch failed: ",
+                hipGetErrorString((hipError_t)status));
     return out;
 #else
     TORCH_CHECK(false, "wva native extension built without HIP support");

@@ -19,11 +19,13 @@
 //   - the default spec geometry (384 = 2 search groups x 3 wave64) runs
 //     the TTFT and ITL bisections concurrently AND speculatively: each
 //     round a group evaluates its bracket's full depth-2 midpoint tree
-//     (bitwise the sequential iterates) and consumes two bisection
-//     levels; wave sync is group-local LDS mailboxes with a watchdog —
-//     no workgroup barriers after the scan;
-//   - LDS budget: (max_k + THREADS + 64) doubles <= 64 KiB for N <= ~700
-//     (the binding routes larger batch limits to the CPU path).
+//     (the midpoints are bitwise the sequential iterates) and consumes
+//     two bisection levels; wave sync is group-local LDS mailboxes with a
+//     watchdog — no workgroup barriers after the scan;
+//   - LDS budget: (max_k + THREADS + 64) doubles <= 64 KiB for N <= ~700;
+//     the launcher checks it for the geometry it picked before launching
+//     and the binding raises when it does not fit (batched.py routes
+//     larger batch limits to the CPU path).
 //
 // Numerics are double throughout, matching the Python analyzer; parity
 // is enforced by tests/test_ops.py, the @gpu numerics tests and
@@ -388,8 +390,11 @@ __device__ void solve_body(const double *__restrict__ prob, double *__restrict__
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
   if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
+  // fails every ordered compare): infeasible, as in queue_host.h
+  if (!(n_rep > 0.0)) return;
   const double rate = total_rate / n_rep;
-  if (rate <= 0.0 || rate > lam_max * 1000.0) return;
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
 
   Stats fin = ev.eval(rate / 1000.0);
   double rho = fin.n_serv / (double)p.max_batch;
@@ -474,8 +479,11 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
   if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
+  // fails every ordered compare): infeasible, as in queue_host.h
+  if (!(n_rep > 0.0)) return;
   const double rate = total_rate / n_rep;
-  if (rate <= 0.0 || rate > lam_max * 1000.0) return;
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
 
   Stats fin = ev.eval(rate / 1000.0);
   double rho = fin.n_serv / (double)p.max_batch;
@@ -502,8 +510,16 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
 // current bracket concurrently — candidate k (heap order) is the
 // midpoint reached after the D halvings encoded by k's bits, computed by
 // the same (lo+hi)/2 recurrence the sequential loop uses, so the
-// iterates are BITWISE identical to wg_binary_search and parity is
-// exact, not approximate.  The group then replays the sequential
+// iterates x are BITWISE identical to wg_binary_search's and, over the
+// same cum table, so is every y and the whole result.  Across geometries
+// the table itself is not the same: build_cum's chunked scan adds log_mu
+// in a THREADS-dependent order once K > 64, which moves y and the
+// outputs by last-place bits (measured <= 2e-14 relative on MI355X; with
+// fp contraction off as well, so that is not the cause) while the
+// decision walk, feasibility and replica counts stay identical.  For
+// K <= 64 every geometry scans one state per thread and the outputs of
+// 64/128/384/896 are bit-identical (tests/test_ops_oracle.py pins both
+// statements).  The group then replays the sequential
 // decision walk on the cached y values, consuming D bisection levels per
 // round: D=2 (SW=3, 384 threads) turns ~100 serial evaluations per
 // target into ~50 rounds, with 6 resident waves per CU hiding the exp
@@ -729,8 +745,11 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
   if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
+  // fails every ordered compare): infeasible, as in queue_host.h
+  if (!(n_rep > 0.0)) return;
   const double rate = total_rate / n_rep;
-  if (rate <= 0.0 || rate > lam_max * 1000.0) return;
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
 
   Stats fin = ev.eval(rate / 1000.0);
   double rho = fin.n_serv / (double)p.max_batch;
@@ -781,8 +800,11 @@ extern "C" __global__ void __launch_bounds__(128) wva_solve_kernel_128(
 #include <cstdlib>
 #include <cstring>
 
-extern "C" void wva_launch_solve(const double *prob, double *out, int n_problems,
-                                 int max_k, void *stream) {
+// Returns 0 on success, -1 when the selected geometry's LDS footprint
+// (cum[max_k] + totals[threads] + 64 slack doubles) exceeds 64 KiB — decided
+// BEFORE anything is launched — or the hipError_t of a failed launch.
+extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
+                                int max_k, void *stream) {
   // Geometry auto-selects on state-chain length (measured:
   // profiles/r01_queue_solver.md, profiles/r01_kernel_sweep.json).  The
   // 2-wave dual kernel overlaps the TTFT and ITL bisections and is the
@@ -820,6 +842,9 @@ extern "C" void wva_launch_solve(const double *prob, double *out, int n_problems
     // (r01 best geometry: 0.175/0.277/0.360; profiles/r02_kernel_geo.json).
     threads = fits(384) ? 384 : 256;
   }
+  // a forced 64/128/256 or the auto pick may still not fit (N > ~715):
+  // refuse here instead of issuing a launch that cannot start
+  if (max_k < 1 || !fits(threads)) return -1;
   const size_t smem = (size_t)(max_k + threads + 64) * sizeof(double);
   if (threads == 64) {
     hipLaunchKernelGGL(wva::wva_solve_kernel_64, dim3(n_problems), dim3(64), smem,
@@ -837,4 +862,5 @@ extern "C" void wva_launch_solve(const double *prob, double *out, int n_problems
     hipLaunchKernelGGL(wva::wva_solve_kernel_256, dim3(n_problems), dim3(256), smem,
                        (hipStream_t)stream, prob, out, n_problems, max_k);
   }
+  return (int)hipGetLastError();
 }

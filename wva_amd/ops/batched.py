@@ -147,7 +147,9 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
             rate_star = metrics.throughput
             total_rate = row[P_TOTAL_RATE]
             n_rep = max(math.ceil(total_rate / rate_star), int(row[P_MIN_REPLICAS]))
-            final = qa.analyze(total_rate / n_rep)
+            if n_rep <= 0:
+                continue  # no replicas: no per-replica rate to analyze
+            final = qa.analyze(total_rate / n_rep)  # rejects rate <= 0
         except AnalyzerError:
             continue
         out[i, R_FEASIBLE] = 1.0
