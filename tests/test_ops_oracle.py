@@ -244,7 +244,10 @@ def _rel(got, exact):
 
 
 def oracle_errors(results, cases):
-    """Per-case errors against the oracle plus the worst of each kind."""
+    """Per-case errors against the oracle plus the worst of each kind.
+
+    A case may carry its own ``final_tol`` (test_ops_oracle_wide.py: the
+    bound grows with the row's log table); without one it is FINAL_TOL."""
     assert results.shape == (len(cases), 6)
     worst = {"rate_known": 0.0, "rate_vs_bound": 0.0, "itl": 0.0, "ttft": 0.0, "rho": 0.0}
     problems = []
@@ -273,10 +276,13 @@ def oracle_errors(results, cases):
             worst["rate_vs_bound"] = max(worst["rate_vs_bound"], rate_err / c["rate_tol"])
             if not rate_err <= c["rate_tol"]:
                 problems.append(f"{tag}: rate_star err {rate_err:.3g} > {c['rate_tol']:.3g}")
+        final_tol = c.get("final_tol", FINAL_TOL)
         for name, err in errs.items():
             worst[name] = max(worst[name], err)
-            if not err <= FINAL_TOL:
-                problems.append(f"{tag}: {name} err {err:.3g} > {FINAL_TOL:g}")
+            if "scale" in c:  # error in units of the row's float64 floor
+                worst["scaled"] = max(worst.get("scaled", 0.0), err / (2.0**-53 * c["scale"]))
+            if not err <= final_tol:
+                problems.append(f"{tag}: {name} err {err:.3g} > {final_tol:.3g}")
     return worst, problems
 
 

@@ -26,19 +26,33 @@ constexpr int kMaxIterations = 100;          // bisection iteration cap
 constexpr int kMaxQueueToBatchRatio = 10;    // K = (1 + ratio) * N
 
 // Problem layout: one row of 12 doubles.
+//
+// Row contract (row_valid below; every solver — this header's host and
+// device users and ops/batched.py's Python path — enforces the same one).
+// A row is valid iff
+//   - every field is finite;
+//   - alpha, beta, gamma, delta >= 0;
+//   - trunc(N) >= 1 and the chain length 11 * N fits an int;
+//   - trunc(out_tokens) >= 1 (and fits an int);
+//   - in_tokens >= 0;
+//   - every target >= 0.
+// An invalid row yields the all-zero result row, as the analyzer's check()
+// methods reject it.  in_tokens, out_tokens, N and min_replicas are
+// truncated toward zero (Python's int()), so a replica count is always
+// integral.
 enum ProblemField {
-  P_ALPHA = 0,    // decode base (ms)
-  P_BETA,         // decode slope (ms per batch unit)
-  P_GAMMA,        // prefill base (ms)
-  P_DELTA,        // prefill slope (ms per token per batch unit)
-  P_IN_TOKENS,    // average input tokens
-  P_OUT_TOKENS,   // average output tokens (K >= 1)
-  P_MAX_BATCH,    // N >= 1
-  P_TARGET_TTFT,  // ms; 0 disables
-  P_TARGET_ITL,   // ms; 0 disables
-  P_TARGET_TPS,   // tokens/s; 0 disables
+  P_ALPHA = 0,    // decode base (ms), >= 0
+  P_BETA,         // decode slope (ms per batch unit), >= 0
+  P_GAMMA,        // prefill base (ms), >= 0
+  P_DELTA,        // prefill slope (ms per token per batch unit), >= 0
+  P_IN_TOKENS,    // average input tokens, >= 0, truncated
+  P_OUT_TOKENS,   // average output tokens, truncated >= 1
+  P_MAX_BATCH,    // N, truncated >= 1
+  P_TARGET_TTFT,  // ms; 0 disables, < 0 invalid
+  P_TARGET_ITL,   // ms; 0 disables, < 0 invalid
+  P_TARGET_TPS,   // tokens/s; 0 disables, < 0 invalid
   P_TOTAL_RATE,   // req/s (> 0; zero-load handled by the host)
-  P_MIN_REPLICAS, // minimum replica count
+  P_MIN_REPLICAS, // minimum replica count, truncated
   PROBLEM_FIELDS
 };
 
@@ -60,6 +74,48 @@ struct Parms {
   int max_batch;   // N
   int num_decode;  // out_tokens-1, or 1 for decode-only single-token
 };
+
+// largest N whose chain length (1 + ratio) * N still fits an int
+constexpr int kMaxBatchLimit = 2147483647 / (1 + kMaxQueueToBatchRatio);
+
+// The row contract above.  Ordered compares are false for NaN, so each
+// test is written to hold only for a proper value.  Branch-free (& rather
+// than && or early returns): the kernels run this before anything else,
+// and nothing in it should make one load wait for another's compare.
+WVA_HD bool row_valid(const double *pr) {
+  bool ok = true;
+  for (int f = 0; f < PROBLEM_FIELDS; ++f) {
+    ok &= fabs(pr[f]) <= 1.7976931348623157e308;  // fails NaN, +-inf
+  }
+  ok &= (pr[P_ALPHA] >= 0.0) & (pr[P_BETA] >= 0.0) & (pr[P_GAMMA] >= 0.0) &
+        (pr[P_DELTA] >= 0.0);
+  ok &= (pr[P_MAX_BATCH] >= 1.0) & (pr[P_MAX_BATCH] < (double)kMaxBatchLimit + 1.0);
+  ok &= (pr[P_OUT_TOKENS] >= 1.0) & (pr[P_OUT_TOKENS] < 2147483648.0);
+  ok &= pr[P_IN_TOKENS] >= 0.0;
+  ok &= (pr[P_TARGET_TTFT] >= 0.0) & (pr[P_TARGET_ITL] >= 0.0) & (pr[P_TARGET_TPS] >= 0.0);
+  return ok;
+}
+
+// Model constants of a VALID row (the int casts are undefined otherwise).
+WVA_HD Parms parms_from_problem(const double *pr) {
+  Parms p;
+  p.alpha = pr[P_ALPHA];
+  p.beta = pr[P_BETA];
+  p.gamma = pr[P_GAMMA];
+  p.delta = pr[P_DELTA];
+  p.in_tokens = trunc(pr[P_IN_TOKENS]);
+  p.out_tokens = (int)pr[P_OUT_TOKENS];
+  p.max_batch = (int)pr[P_MAX_BATCH];
+  p.num_decode = p.out_tokens - 1;
+  if (p.in_tokens == 0.0 && p.out_tokens == 1) p.num_decode = 1;
+  return p;
+}
+
+// Chain length K = 11 * N of a row; 0 for an invalid row, which needs no
+// table at all.
+WVA_HD int row_chain_length(const double *pr) {
+  return row_valid(pr) ? (int)pr[P_MAX_BATCH] * (1 + kMaxQueueToBatchRatio) : 0;
+}
 
 WVA_HD double prefill_time(const Parms &p, double batch) {
   return p.in_tokens == 0.0 ? 0.0 : p.gamma + p.delta * p.in_tokens * batch;

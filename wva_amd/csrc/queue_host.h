@@ -61,22 +61,12 @@ inline int binary_search_host(double x_min, double x_max, double y_target, F eva
   return 0;
 }
 
-inline Parms parms_from_problem(const double *pr) {
-  Parms p;
-  p.alpha = pr[P_ALPHA];
-  p.beta = pr[P_BETA];
-  p.gamma = pr[P_GAMMA];
-  p.delta = pr[P_DELTA];
-  p.in_tokens = pr[P_IN_TOKENS];
-  p.out_tokens = (int)pr[P_OUT_TOKENS];
-  p.max_batch = (int)pr[P_MAX_BATCH];
-  p.num_decode = p.out_tokens - 1;
-  if (p.in_tokens == 0.0 && p.out_tokens == 1) p.num_decode = 1;
-  return p;
-}
-
-// Scalar solve of one problem (CPU path).  cum must hold K doubles.
+// Scalar solve of one problem (CPU path).  cum must hold
+// row_chain_length(pr) doubles; a row that breaks the contract of
+// queue_core.h yields the all-zero row and touches no table.
 inline void solve_one(const double *pr, double *out, double *cum) {
+  for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
+  if (!row_valid(pr)) return;
   Parms p = parms_from_problem(pr);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
@@ -90,8 +80,6 @@ inline void solve_one(const double *pr, double *out, double *cum) {
 
   auto eval_ttft = [&](double lam) { return eval_ttft_of(p, eval_model(p, cum, K, lam)); };
   auto eval_itl = [&](double lam) { return eval_itl_of(p, eval_model(p, cum, K, lam)); };
-
-  for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
 
   double lam_ttft = lam_max;
   if (pr[P_TARGET_TTFT] > 0.0) {
@@ -112,7 +100,8 @@ inline void solve_one(const double *pr, double *out, double *cum) {
 
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
-  if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
   // no replicas, or a per-replica rate that is not > 0 (zero or negative
   // load; NaN from 0/0 fails every ordered compare): infeasible
   if (!(n_rep > 0.0)) return;

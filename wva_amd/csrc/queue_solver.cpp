@@ -16,6 +16,7 @@
 #include <c10/hip/HIPStream.h>
 #endif
 
+#include <climits>
 #include <cmath>
 #include <vector>
 
@@ -45,10 +46,19 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
     if (max_k_hint > 0) {
       // caller-supplied chain length (hipGraph capture cannot tolerate
       // the .item() device sync below; wva_amd/ops/batched.py computes
-      // it host-side from the numpy batch before upload)
-      max_k = (int)max_k_hint;
+      // it host-side from the numpy batch before upload).  The hint is
+      // the LDS the launch reserves for the cumulative table; the kernels
+      // check every row against it, so a hint that is too small for a row
+      // yields the all-zero infeasible row for it, not corruption.
+      max_k = max_k_hint > INT_MAX ? INT_MAX : (int)max_k_hint;
     } else {
-      const double max_batch = problems.select(1, wva::P_MAX_BATCH).max().item<double>();
+      // largest N among the rows whose N is in the valid range: a NaN,
+      // infinite or out-of-range N is an invalid row (queue_core.h) and
+      // must not size the launch
+      auto n = problems.select(1, wva::P_MAX_BATCH);
+      auto in_range = n.ge(1.0).logical_and(n.lt((double)wva::kMaxBatchLimit + 1.0));
+      const double max_batch =
+          torch::where(in_range, n, torch::ones_like(n)).max().item<double>();
       max_k = (int)max_batch * (1 + wva::kMaxQueueToBatchRatio);
     }
     auto stream = c10::hip::getCurrentHIPStream();
@@ -72,8 +82,7 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
   // scratch sized by the largest K in the batch
   int max_k = 1;
   for (int64_t i = 0; i < B; ++i) {
-    int k = (int)pr[i * wva::PROBLEM_FIELDS + wva::P_MAX_BATCH] *
-            (1 + wva::kMaxQueueToBatchRatio);
+    int k = wva::row_chain_length(pr + i * wva::PROBLEM_FIELDS);  // 0 if invalid
     if (k > max_k) max_k = k;
   }
   at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {

@@ -30,8 +30,7 @@ static py::array_t<double> solve_allocations(
 
   int max_k = 1;
   for (ssize_t i = 0; i < B; ++i) {
-    int k = (int)pr[i * wva::PROBLEM_FIELDS + wva::P_MAX_BATCH] *
-            (1 + wva::kMaxQueueToBatchRatio);
+    int k = wva::row_chain_length(pr + i * wva::PROBLEM_FIELDS);  // 0 if invalid
     if (k > max_k) max_k = k;
   }
 

@@ -22,6 +22,10 @@
 //     (the midpoints are bitwise the sequential iterates) and consumes
 //     two bisection levels; wave sync is group-local LDS mailboxes with a
 //     watchdog — no workgroup barriers after the scan;
+//   - every body starts with the row guard (row_rejected): a row that
+//     breaks the contract of queue_core.h, or whose chain exceeds the
+//     max_k this launch reserved, gets the all-zero row before LDS is
+//     touched;
 //   - LDS budget: (max_k + THREADS + 64) doubles <= 64 KiB for N <= ~700;
 //     the launcher checks it for the geometry it picked before launching
 //     and the binding raises when it does not fit (batched.py routes
@@ -306,18 +310,15 @@ __device__ int wg_binary_search(double x_min, double x_max, double y_target, F e
   return 0;
 }
 
-__device__ inline Parms load_parms(const double *pr) {
-  Parms p;
-  p.alpha = pr[P_ALPHA];
-  p.beta = pr[P_BETA];
-  p.gamma = pr[P_GAMMA];
-  p.delta = pr[P_DELTA];
-  p.in_tokens = pr[P_IN_TOKENS];
-  p.out_tokens = (int)pr[P_OUT_TOKENS];
-  p.max_batch = (int)pr[P_MAX_BATCH];
-  p.num_decode = p.out_tokens - 1;
-  if (p.in_tokens == 0.0 && p.out_tokens == 1) p.num_decode = 1;
-  return p;
+// Row guard shared by the three bodies, taken before anything touches
+// LDS: a row that breaks the contract of queue_core.h (row_valid), or whose
+// chain does not fit the max_k doubles this launch reserved for cum, gets
+// the all-zero result row.  Every thread of the workgroup reads the same
+// row, so the early return is uniform and precedes the first barrier.
+__device__ inline bool row_rejected(const double *pr, double *res, int max_k) {
+  const bool ok = row_valid(pr) && row_chain_length(pr) <= max_k;
+  if (!ok && threadIdx.x < RESULT_FIELDS) res[threadIdx.x] = 0.0;
+  return !ok;
 }
 
 // chunked parallel inclusive scan of log_mu over K states into LDS
@@ -349,7 +350,8 @@ __device__ void solve_body(const double *__restrict__ prob, double *__restrict__
   double *res = out + (size_t)pid * RESULT_FIELDS;
   const int tid = threadIdx.x;
 
-  const Parms p = load_parms(pr);
+  if (row_rejected(pr, res, max_k)) return;
+  const Parms p = parms_from_problem(pr);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
@@ -389,7 +391,8 @@ __device__ void solve_body(const double *__restrict__ prob, double *__restrict__
 
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
-  if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
   // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
   // fails every ordered compare): infeasible, as in queue_host.h
   if (!(n_rep > 0.0)) return;
@@ -429,7 +432,8 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
 
-  const Parms p = load_parms(pr);
+  if (row_rejected(pr, res, max_k)) return;
+  const Parms p = parms_from_problem(pr);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
@@ -478,7 +482,8 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
 
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
-  if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
   // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
   // fails every ordered compare): infeasible, as in queue_host.h
   if (!(n_rep > 0.0)) return;
@@ -687,7 +692,8 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
   const int sub = wave % SW;
   const int lane = tid & 63;
 
-  const Parms p = load_parms(pr);
+  if (row_rejected(pr, res, max_k)) return;
+  const Parms p = parms_from_problem(pr);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
@@ -744,7 +750,8 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
 
   const double total_rate = pr[P_TOTAL_RATE];
   double n_rep = ceil(total_rate / rate_star);
-  if (n_rep < pr[P_MIN_REPLICAS]) n_rep = pr[P_MIN_REPLICAS];
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
   // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
   // fails every ordered compare): infeasible, as in queue_host.h
   if (!(n_rep > 0.0)) return;

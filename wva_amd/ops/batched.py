@@ -9,7 +9,19 @@ gfx950 HIP kernel — one workgroup per pair) or by the pure-Python
 analyzer fallback; mg1 mode routes through the scalar analyzer with
 per-server cs^2 support.
 
-Field layouts mirror wva_amd/csrc/queue_core.h.
+Field layouts mirror wva_amd/csrc/queue_core.h, and so does the row
+contract (``row_valid`` there, ``valid_rows`` here).  A row is valid iff
+
+- every field is finite;
+- alpha, beta, gamma, delta >= 0;
+- trunc(N) >= 1 and the chain length 11 * N fits a C int;
+- trunc(out_tokens) >= 1 (and fits a C int);
+- in_tokens >= 0;
+- every target >= 0.
+
+An invalid row yields the all-zero result row in every implementation, as
+the analyzer's ``check()`` methods reject it.  in_tokens, out_tokens, N and
+min_replicas are truncated toward zero, so replica counts are integral.
 """
 
 from __future__ import annotations
@@ -46,6 +58,23 @@ RESULT_FIELDS = 6
 
 # the GPU path keeps the cumulative table in LDS: N <= ~700
 GPU_MAX_BATCH_LIMIT = 700
+
+# largest N whose chain length 11 * N fits a C int (queue_core.h kMaxBatchLimit)
+_MAX_BATCH_LIMIT = (2**31 - 1) // (1 + MAX_QUEUE_TO_BATCH_RATIO)
+
+
+def valid_rows(problems: np.ndarray) -> np.ndarray:
+    """Boolean mask of the rows that satisfy the row contract (module
+    docstring); the same predicate as ``row_valid`` in csrc/queue_core.h."""
+    p = problems
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(p).all(axis=1)
+        ok &= (p[:, P_ALPHA : P_DELTA + 1] >= 0).all(axis=1)
+        ok &= (p[:, P_MAX_BATCH] >= 1) & (p[:, P_MAX_BATCH] < _MAX_BATCH_LIMIT + 1)
+        ok &= (p[:, P_OUT_TOKENS] >= 1) & (p[:, P_OUT_TOKENS] < 2.0**31)
+        ok &= p[:, P_IN_TOKENS] >= 0
+        ok &= (p[:, P_TARGET_TTFT : P_TARGET_TPS + 1] >= 0).all(axis=1)
+    return ok
 
 # hipGraph dispatch cache: repeated fleet solves of the same shape replay
 # a captured graph instead of re-launching.  Keyed by (B, max_k); replays
@@ -118,7 +147,10 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
     per-row array (mg1 auto mode derives one per server)."""
     scv_arr = np.broadcast_to(np.asarray(scv, dtype=np.float64), (problems.shape[0],))
     out = np.zeros((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
+    valid = valid_rows(problems)
     for i, row in enumerate(problems):
+        if not valid[i]:
+            continue  # all-zero row; also keeps int() off NaN and inf
         N = int(row[P_MAX_BATCH])
         config = Configuration(
             max_batch_size=N,
@@ -200,17 +232,25 @@ def solve_problems(problems: np.ndarray, device: Optional[str] = None) -> np.nda
         native = get_native()  # raises loudly if missing on a GPU box
         import torch
 
-        max_batch = problems[:, P_MAX_BATCH].max()
+        # the kernel's row guard turns invalid rows into zero rows, so they
+        # ride along; only when the largest N is a NaN or past the LDS
+        # limit is the predicate needed here, to keep invalid rows from
+        # sizing the launch or being sent to the CPU path
+        batch_limits = problems[:, P_MAX_BATCH]
+        max_batch = batch_limits.max()
+        if not max_batch <= GPU_MAX_BATCH_LIMIT:
+            batch_limits = np.where(valid_rows(problems), batch_limits, 1.0)
+            max_batch = batch_limits.max()
         if max_batch > GPU_MAX_BATCH_LIMIT:
             # LDS-resident limit: solve oversized problems on CPU
-            big = problems[:, P_MAX_BATCH] > GPU_MAX_BATCH_LIMIT
+            big = batch_limits > GPU_MAX_BATCH_LIMIT
             out = np.empty((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
             out[~big] = solve_problems(problems[~big], device=device)
             out[big] = solve_problems(problems[big], device="cpu")
             return out
         # chain length computed host-side (also feeds hipGraph capture,
         # where the binding's device-sync fallback is illegal)
-        max_k = int(max_batch) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
+        max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
         t = torch.from_numpy(problems).to(device)
         res = _graph_solve(native, t, max_k)
         if res is not None:
