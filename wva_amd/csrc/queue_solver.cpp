@@ -29,6 +29,10 @@
 // launched); otherwise the hipError_t of the failed launch
 extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
                                 int max_k, void *stream);
+
+// submit/collect on numpy arrays: the asynchronous, copy-light way into
+// the same launcher (what wva_amd/ops/batched.py uses on the GPU)
+#include "sizing_dispatch.h"
 #endif
 
 static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hint = -1) {
@@ -37,7 +41,11 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
   TORCH_CHECK(problems.scalar_type() == torch::kFloat64, "problems must be float64");
   problems = problems.contiguous();
   const int64_t B = problems.size(0);
-  auto out = torch::zeros({B, (int64_t)wva::RESULT_FIELDS}, problems.options());
+  // the GPU kernels write all six fields of every row (rejected rows
+  // included), so only the CPU path needs a zeroed output
+  auto out = problems.is_cuda()
+                 ? torch::empty({B, (int64_t)wva::RESULT_FIELDS}, problems.options())
+                 : torch::zeros({B, (int64_t)wva::RESULT_FIELDS}, problems.options());
   if (B == 0) return out;
 
   if (problems.is_cuda()) {
@@ -103,6 +111,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
 #ifdef WVA_WITH_HIP
+  m.def("submit", &wva::dispatch::submit,
+        "Enqueue upload, sizing kernel and download for a float64 [B, 12] "
+        "numpy array on the private dispatch stream; returns a ticket "
+        "without waiting",
+        pybind11::arg("problems"), pybind11::arg("max_k"));
+  m.def("collect", &wva::dispatch::collect,
+        "Wait (GIL released) for a ticket and return its float64 [B, 6] results",
+        pybind11::arg("ticket"));
+  m.def("dispatch_pool_stats", &wva::dispatch::pool_stats,
+        "(slots, slots in flight) of the dispatch pool");
   m.attr("HAS_HIP") = true;
 #else
   m.attr("HAS_HIP") = false;

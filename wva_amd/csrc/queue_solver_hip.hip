@@ -507,8 +507,9 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
 // ---------------------------------------------------------------------------
 // Speculative-tree multisection ("spec") kernel — round-2 lever
 // (profiles/r01_rocprof_pmc.txt: ~32% of wave time parked at barriers and
-// ~34% issue-stalled on the fp64 exp/log chain of ~200 SEQUENTIAL model
-// evaluations; the bisection itself is the critical path).
+// ~34% issue-stalled on the fp64 exp/log chain of the SEQUENTIAL model
+// evaluations, up to 30 per target; the bisection itself is the critical
+// path).
 //
 // Geometry: 2 search groups (TTFT, ITL) x SW waves, SW = 2^D - 1.  Each
 // round every group evaluates the ENTIRE depth-D midpoint tree of its
@@ -526,9 +527,13 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
 // 64/128/384/896 are bit-identical (tests/test_ops_oracle.py pins both
 // statements).  The group then replays the sequential
 // decision walk on the cached y values, consuming D bisection levels per
-// round: D=2 (SW=3, 384 threads) turns ~100 serial evaluations per
-// target into ~50 rounds, with 6 resident waves per CU hiding the exp
-// chain latency the PMC profile flagged.
+// round: D=2 (SW=3, 384 threads) halves the serial rounds per target.
+// kMaxIterations = 100 is only the cap: the 1e-6 stop ends a search after
+// at most 30 evaluations (two of them the bracket ends; median 22) on the
+// flagship benchmark's rows, counted with the Python analyzer on 1536 of
+// them — so a target costs about one pre-phase round plus <= 14 tree
+// rounds here.  6 resident waves per CU hide the exp chain latency the
+// PMC profile flagged.
 //
 // Wave synchronization is group-local LDS mailboxes (publish y, fence,
 // bump flag; consumers spin with s_sleep) — NO workgroup barriers after

@@ -7,7 +7,10 @@ the fleet are packed into one [B, 12] float64 matrix and solved either by
 the native extension (the torch-free C++/OpenMP binding on CPU, or the
 gfx950 HIP kernel — one workgroup per pair) or by the pure-Python
 analyzer fallback; mg1 mode routes through the scalar analyzer with
-per-server cs^2 support.
+per-server cs^2 support.  On the GPU the matrix travels through the native
+submit/collect dispatch (csrc/sizing_dispatch.h), and
+``BatchedAllocationSolver`` may cut the fleet into chunks so that its own
+per-row host work overlaps the launches (docs/design/native-queue-solver.md).
 
 Field layouts mirror wva_amd/csrc/queue_core.h, and so does the row
 contract (``row_valid`` there, ``valid_rows`` here).  A row is valid iff
@@ -26,7 +29,9 @@ min_replicas are truncated toward zero, so replica counts are integral.
 
 from __future__ import annotations
 
+import contextlib
 import math
+import os
 from typing import Dict, List, Optional, Tuple
 
 import numpy as np
@@ -90,10 +95,26 @@ _graph_disabled = False
 _mg1_warned = False
 
 
+def _graph_requested() -> bool:
+    return not _graph_disabled and os.environ.get("WVA_GPU_GRAPH", "0") == "1"
+
+
+_NO_DEVICE_SWITCH = contextlib.nullcontext()
+
+
+def _on_device(device):
+    """Context that makes ``device`` current for the native dispatch (which
+    runs on the current device); plain "cuda" already is."""
+    if str(device) == "cuda":
+        return _NO_DEVICE_SWITCH
+    import torch
+
+    return torch.cuda.device(torch.device(device))
+
+
 def _graph_solve(native, problems_t, max_k):
     """Solve via a cached hipGraph; None -> caller uses plain dispatch."""
     global _graph_lock, _graph_disabled
-    import os
     import threading
 
     if _graph_disabled or os.environ.get("WVA_GPU_GRAPH", "0") != "1":
@@ -251,11 +272,15 @@ def solve_problems(problems: np.ndarray, device: Optional[str] = None) -> np.nda
         # chain length computed host-side (also feeds hipGraph capture,
         # where the binding's device-sync fallback is illegal)
         max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
-        t = torch.from_numpy(problems).to(device)
-        res = _graph_solve(native, t, max_k)
-        if res is not None:
-            return res
-        return native.solve_allocations(t, max_k).cpu().numpy()
+        if _graph_requested():
+            t = torch.from_numpy(problems).to(device)
+            res = _graph_solve(native, t, max_k)
+            if res is not None:
+                return res
+        # lean dispatch (csrc/sizing_dispatch.h): pinned staging, no output
+        # fill, no tensors — here as one chunk, submitted and collected
+        with _on_device(device):
+            return native.collect(native.submit(problems, max_k))
 
     from . import get_native_cpu, native_cpu_available
 
@@ -277,17 +302,120 @@ def solve_problems(problems: np.ndarray, device: Optional[str] = None) -> np.nda
     return _solve_problems_python(problems)
 
 
+class SyncDispatch:
+    """submit/collect over today's synchronous ``solve_problems``: ``submit``
+    solves on the spot and the ticket is the result.  Runs the chunked
+    pipeline on any device, and carries the M/G/1 routing: ``global_scv`` is
+    given when some server may need the corrected analyzer, and ``submit``
+    then decides from the rows' cs^2 values."""
+
+    def __init__(self, device: Optional[str], global_scv: Optional[float] = None) -> None:
+        self.device = device
+        self.global_scv = global_scv
+
+    def submit(self, problems: np.ndarray, scv_rows=None):
+        if self.global_scv is not None:
+            scv_arr = np.array(
+                [s if s >= 0 else self.global_scv for s in scv_rows], dtype=np.float64
+            )
+            if (scv_arr != 1.0).any():
+                # M/G/1-corrected sizing (global mg1 mode and/or
+                # per-server measured cs^2): the scalar analyzer path
+                return _solve_problems_python(problems, scv=scv_arr)
+        return solve_problems(problems, self.device)
+
+    def collect(self, ticket) -> np.ndarray:
+        return ticket
+
+
+class NativeGpuDispatch:
+    """submit/collect over the native asynchronous dispatch
+    (csrc/sizing_dispatch.h): ``submit`` returns once upload, kernel and
+    download are enqueued, ``collect`` waits for them.  A chunk that needs
+    the oversized-N split to the CPU is solved synchronously instead."""
+
+    def __init__(self, native, device: str) -> None:
+        self.native = native
+        self.device = device
+
+    def submit(self, problems: np.ndarray, scv_rows=None):
+        max_batch = problems[:, P_MAX_BATCH].max()
+        if not max_batch <= GPU_MAX_BATCH_LIMIT:  # also a NaN N
+            return None, solve_problems(problems, self.device)
+        max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
+        with _on_device(self.device):
+            return self.native.submit(problems, max_k), None
+
+    def collect(self, ticket) -> np.ndarray:
+        native_ticket, solved = ticket
+        if native_ticket is None:
+            return solved
+        return self.native.collect(native_ticket)
+
+
+# Chunks the GPU pipeline splits a fleet into when the caller does not say
+# (measured on the flagship shape: profiles/async_dispatch.md).
+DEFAULT_GPU_CHUNKS = 2
+
+# The launcher picks the chip-filling geometry from this many rows on
+# (wva_launch_solve); a fleet that could reach it is never chunked on the
+# GPU, so every chunk runs the geometry the whole batch would have run.
+_GPU_CHUNKING_ROW_BOUND = 512
+
+
 class BatchedAllocationSolver:
     """Batched analyze phase: computes ``server.all_allocations`` for every
-    server in a System in one native call (semantically equal to
-    ``System.calculate()``)."""
+    server in a System through the native solver (semantically equal to
+    ``System.calculate()``).
 
-    def __init__(self, device: Optional[str] = None) -> None:
+    The servers are cut into ``chunks`` contiguous slices and driven as a
+    pipeline over a submit/collect dispatch: build the rows of slice i,
+    submit them, then collect slice i-1 and turn its results into
+    Allocations.  On the GPU the host work of one slice overlaps the
+    launch of another; results do not depend on the chunk count (rows are
+    solved independently, and the GPU path chunks only while every chunk
+    auto-selects the kernel geometry of the whole batch).  ``chunks=None``
+    picks DEFAULT_GPU_CHUNKS on the GPU and 1 elsewhere; 1 is a single
+    call.  A fleet in which some server may take the M/G/1-corrected
+    analyzer is solved as one chunk, the routing decided from all its rows.
+    """
+
+    def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None) -> None:
+        if chunks is not None and chunks < 1:
+            raise ValueError("chunks must be at least 1")
         self.device = device
+        self.chunks = chunks
+
+    def _plan(self, system: System, servers):
+        """The dispatch and chunk count for this fleet, decided before any
+        submit; also whether rows must carry their server's cs^2."""
+        from ..analyzer.mg1 import configured_scv
+
+        global_scv = configured_scv()
+        if global_scv != 1.0 or any(
+            s >= 0 and s != 1.0 for s in [getattr(v, "service_scv", -1.0) for v in servers]
+        ):
+            return SyncDispatch(self.device, global_scv), 1, True
+        want_gpu = self.device is not None and str(self.device).startswith("cuda")
+        if want_gpu and not _graph_requested():
+            from . import get_native
+
+            native = get_native()  # raises loudly if missing on a GPU box
+            if native is None or not native.HAS_HIP:
+                raise RuntimeError("the native HIP extension is required for device "
+                                   f"{self.device!r} and is not built")
+            chunks = self.chunks if self.chunks is not None else DEFAULT_GPU_CHUNKS
+            if len(servers) * len(system.accelerators) >= _GPU_CHUNKING_ROW_BOUND:
+                chunks = 1
+            return NativeGpuDispatch(native, self.device), chunks, False
+        return SyncDispatch(self.device), self.chunks or 1, False
 
     def calculate(self, system: System) -> None:
         for g in system.accelerators.values():
             g.calculate()
+
+        all_servers = list(system.servers.values())
+        dispatch, n_chunks, track_scv = self._plan(system, all_servers)
 
         # pre-resolve the per-(model, accelerator) constants once — fleets
         # repeat model/accelerator combinations heavily
@@ -317,79 +445,7 @@ class BatchedAllocationSolver:
         from ..core.allocation import sizing_headroom
 
         headroom_factor = 1.0 + sizing_headroom()
-        rows: List[Tuple[float, ...]] = []
-        keys: List[Tuple[str, str, int]] = []  # (server, acc, N)
-        zero_load: Dict[str, Dict[str, Allocation]] = {}
-        costs: List[float] = []
-        scv_rows: List[float] = []  # per-server cs^2 (negative = use global)
-        rows_append, keys_append, costs_append = rows.append, keys.append, costs.append
-        scv_append = scv_rows.append
-
-        for server in system.servers.values():
-            server.all_allocations = {}
-            load = server.load
-            if (
-                load is None
-                or load.arrival_rate < 0
-                or load.avg_in_tokens < 0
-                or load.avg_out_tokens < 0
-            ):
-                continue
-            model = system.model(server.model_name)
-            if model is None:
-                continue
-            svc = system.service_class(server.service_class_name)
-            if svc is None:
-                continue
-            target = svc.model_target(server.model_name)
-            if target is None:
-                continue
-            target_ttft, target_itl, target_tps = target.ttft, target.itl, target.tps
-            arrival, in_tok, out_tok = load.arrival_rate, load.avg_in_tokens, load.avg_out_tokens
-            server_name = server.name
-            server_max_batch = server.max_batch_size
-            min_replicas = float(server.min_num_replicas)
-            candidates = server.get_candidate_accelerators(system.accelerators)
-            for acc in candidates.values():
-                info = pair_info(model, acc)
-                if info is None:
-                    continue
-                if arrival == 0 or out_tok == 0:
-                    perf = model.get_perf_data(acc.name)
-                    alloc = _zero_load_allocation(server, model, acc, perf)
-                    zero_load.setdefault(server_name, {})[acc.name] = alloc
-                    continue
-                alpha, beta, gamma, delta, perf_max_batch, at_tokens, cost_per_rep = info
-                K = int(out_tok)
-                N = server_max_batch if server_max_batch > 0 else max(perf_max_batch * at_tokens // K, 1)
-                total_rate = (
-                    arrival / 60.0 if target_tps == 0 else target_tps / float(K)
-                ) * headroom_factor
-                rows_append(
-                    (alpha, beta, gamma, delta, float(int(in_tok)), float(K), float(N),
-                     target_ttft, target_itl, target_tps, total_rate, min_replicas)
-                )
-                keys_append((server_name, acc.name, N))
-                costs_append(cost_per_rep)
-                scv_append(getattr(server, "service_scv", -1.0))
-
-        if rows:
-            arr = np.array(rows, dtype=np.float64)
-            from ..analyzer.mg1 import configured_scv
-
-            global_scv = configured_scv()
-            scv_arr = np.array(
-                [s if s >= 0 else global_scv for s in scv_rows], dtype=np.float64
-            )
-            if (scv_arr != 1.0).any():
-                # M/G/1-corrected sizing (global mg1 mode and/or
-                # per-server measured cs^2): the scalar analyzer path
-                results = _solve_problems_python(arr, scv=scv_arr)
-            else:
-                results = solve_problems(arr, self.device)
-        else:
-            results = np.zeros((0, RESULT_FIELDS))
-
+        accelerators = system.accelerators
         opt_spec = system.optimizer_spec
         energy_enabled = (
             opt_spec is not None
@@ -397,33 +453,133 @@ class BatchedAllocationSolver:
             and opt_spec.energy_cost_per_kwh > 0
         )
         servers = system.servers
-        results_list = results.tolist()  # plain floats beat numpy scalar access
-        for (server_name, acc_name, N), res, cost_per_replica in zip(keys, results_list, costs):
-            if res[R_FEASIBLE] != 1.0:
-                continue
-            server = servers[server_name]
-            num_replicas = int(res[R_REPLICAS])
-            alloc = Allocation(
-                accelerator=acc_name,
-                num_replicas=num_replicas,
-                batch_size=N,
-                cost=cost_per_replica * num_replicas,
-                itl=res[R_ITL],
-                ttft=res[R_TTFT],
-                rho=res[R_RHO],
-                max_arrv_rate_per_replica=res[R_RATE_STAR] / 1000.0,
-            )
-            cur = server.cur_allocation
-            alloc.value = cur.transition_penalty(alloc) if cur is not None else alloc.cost
-            if energy_enabled:
-                alloc.value += energy_value_term(system, server, alloc)
-            server.all_allocations[acc_name] = alloc
 
-        for server_name, accs in zero_load.items():
-            server = servers[server_name]
-            for acc_name, alloc in accs.items():
-                if server.cur_allocation is not None:
-                    alloc.set_value(server.cur_allocation.transition_penalty(alloc))
+        def build_rows(chunk_servers):
+            """Build and submit the rows of one slice of servers; returns
+            what apply_results needs once they are solved."""
+            rows: List[Tuple[float, ...]] = []
+            keys: List[Tuple[str, str, int]] = []  # (server, acc, N)
+            zero_load: Dict[str, Dict[str, Allocation]] = {}
+            costs: List[float] = []
+            scv_rows: List[float] = []  # per-server cs^2 (negative = use global)
+            rows_append, keys_append, costs_append = rows.append, keys.append, costs.append
+            scv_append = scv_rows.append
+
+            for server in chunk_servers:
+                server.all_allocations = {}
+                load = server.load
+                if (
+                    load is None
+                    or load.arrival_rate < 0
+                    or load.avg_in_tokens < 0
+                    or load.avg_out_tokens < 0
+                ):
+                    continue
+                model = system.model(server.model_name)
+                if model is None:
+                    continue
+                svc = system.service_class(server.service_class_name)
+                if svc is None:
+                    continue
+                target = svc.model_target(server.model_name)
+                if target is None:
+                    continue
+                target_ttft, target_itl, target_tps = target.ttft, target.itl, target.tps
+                arrival, in_tok, out_tok = load.arrival_rate, load.avg_in_tokens, load.avg_out_tokens
+                server_name = server.name
+                server_max_batch = server.max_batch_size
+                min_replicas = float(server.min_num_replicas)
+                candidates = server.get_candidate_accelerators(accelerators)
+                for acc in candidates.values():
+                    info = pair_info(model, acc)
+                    if info is None:
+                        continue
+                    if arrival == 0 or out_tok == 0:
+                        perf = model.get_perf_data(acc.name)
+                        alloc = _zero_load_allocation(server, model, acc, perf)
+                        zero_load.setdefault(server_name, {})[acc.name] = alloc
+                        continue
+                    alpha, beta, gamma, delta, perf_max_batch, at_tokens, cost_per_rep = info
+                    K = int(out_tok)
+                    N = server_max_batch if server_max_batch > 0 else max(perf_max_batch * at_tokens // K, 1)
+                    total_rate = (
+                        arrival / 60.0 if target_tps == 0 else target_tps / float(K)
+                    ) * headroom_factor
+                    rows_append(
+                        (alpha, beta, gamma, delta, float(int(in_tok)), float(K), float(N),
+                         target_ttft, target_itl, target_tps, total_rate, min_replicas)
+                    )
+                    keys_append((server_name, acc.name, N))
+                    costs_append(cost_per_rep)
+                    if track_scv:
+                        scv_append(getattr(server, "service_scv", -1.0))
+
+            ticket = None
+            if rows:
+                ticket = dispatch.submit(np.array(rows, dtype=np.float64), scv_rows)
+            return ticket, keys, costs, zero_load
+
+        def apply_results(ticket, keys, costs, zero_load):
+            """Collect one slice and turn its results into Allocations."""
+            if ticket is not None:
+                # plain floats beat numpy scalar access
+                results_list = dispatch.collect(ticket).tolist()
+            else:
+                results_list = []
+            for (server_name, acc_name, N), res, cost_per_replica in zip(keys, results_list, costs):
+                if res[R_FEASIBLE] != 1.0:
+                    continue
+                server = servers[server_name]
+                num_replicas = int(res[R_REPLICAS])
+                alloc = Allocation(
+                    accelerator=acc_name,
+                    num_replicas=num_replicas,
+                    batch_size=N,
+                    cost=cost_per_replica * num_replicas,
+                    itl=res[R_ITL],
+                    ttft=res[R_TTFT],
+                    rho=res[R_RHO],
+                    max_arrv_rate_per_replica=res[R_RATE_STAR] / 1000.0,
+                )
+                cur = server.cur_allocation
+                alloc.value = cur.transition_penalty(alloc) if cur is not None else alloc.cost
                 if energy_enabled:
-                    alloc.set_value(alloc.value + energy_value_term(system, server, alloc))
+                    alloc.value += energy_value_term(system, server, alloc)
                 server.all_allocations[acc_name] = alloc
+
+            for server_name, accs in zero_load.items():
+                server = servers[server_name]
+                for acc_name, alloc in accs.items():
+                    if server.cur_allocation is not None:
+                        alloc.set_value(server.cur_allocation.transition_penalty(alloc))
+                    if energy_enabled:
+                        alloc.set_value(alloc.value + energy_value_term(system, server, alloc))
+                    server.all_allocations[acc_name] = alloc
+
+        # contiguous, near-equal slices of the servers; empty ones (more
+        # chunks than servers) are skipped
+        n = len(all_servers)
+        bounds = [n * i // n_chunks for i in range(n_chunks + 1)]
+        pending = None
+        try:
+            for lo, hi in zip(bounds, bounds[1:]):
+                if lo == hi:
+                    continue
+                submitted = build_rows(all_servers[lo:hi])
+                if pending is not None:
+                    previous, pending = pending, submitted
+                    apply_results(*previous)
+                else:
+                    pending = submitted
+            if pending is not None:
+                last, pending = pending, None
+                apply_results(*last)
+        finally:
+            # an exception between submit and collect must not leave a
+            # launch uncollected (its slot would stay busy for good)
+            if pending is not None and pending[0] is not None:
+                try:
+                    dispatch.collect(pending[0])
+                except Exception:
+                    pass
+
