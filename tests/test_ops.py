@@ -118,8 +118,10 @@ class TestBatchedSystemParity:
                 x, y = sa[acc], ba[acc]
                 assert x.num_replicas == y.num_replicas
                 assert x.batch_size == y.batch_size
-                np.testing.assert_allclose(x.cost, y.cost, rtol=1e-6)
-                np.testing.assert_allclose(x.value, y.value, rtol=1e-6, atol=1e-9)
+                # same association of cost * (instances * replicas): bit-equal,
+                # or an exact cost tie is broken differently (test_cycle_oracle.py)
+                assert x.cost == y.cost
+                assert x.value == y.value
                 np.testing.assert_allclose(x.itl, y.itl, rtol=1e-4)
                 np.testing.assert_allclose(x.ttft, y.ttft, rtol=1e-4, atol=1e-6)
                 np.testing.assert_allclose(

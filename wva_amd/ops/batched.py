@@ -366,7 +366,8 @@ _GPU_CHUNKING_ROW_BOUND = 512
 class BatchedAllocationSolver:
     """Batched analyze phase: computes ``server.all_allocations`` for every
     server in a System through the native solver (semantically equal to
-    ``System.calculate()``).
+    ``System.calculate()``: same candidate order, batch size, cost and value
+    bit for bit — tests/test_cycle_oracle.py).
 
     The servers are cut into ``chunks`` contiguous slices and driven as a
     pipeline over a submit/collect dispatch: build the rows of slice i,
@@ -419,7 +420,7 @@ class BatchedAllocationSolver:
 
         # pre-resolve the per-(model, accelerator) constants once — fleets
         # repeat model/accelerator combinations heavily
-        pair_cache: Dict[Tuple[str, str], Optional[Tuple[float, float, float, float, int, int, float]]] = {}
+        pair_cache: Dict[Tuple[str, str], Optional[Tuple[float, float, float, float, int, int, float, int]]] = {}
 
         def pair_info(model, acc):
             key = (model.name, acc.name)
@@ -437,7 +438,8 @@ class BatchedAllocationSolver:
                 perf.prefill_parms.delta,
                 perf.max_batch_size,
                 perf.at_tokens,
-                acc.cost * model.get_num_instances(acc.name),
+                acc.cost,
+                model.get_num_instances(acc.name),
             )
             pair_cache[key] = info
             return info
@@ -458,11 +460,11 @@ class BatchedAllocationSolver:
             """Build and submit the rows of one slice of servers; returns
             what apply_results needs once they are solved."""
             rows: List[Tuple[float, ...]] = []
-            keys: List[Tuple[str, str, int]] = []  # (server, acc, N)
+            # (server, acc, N, unit cost, instances per replica)
+            keys: List[Tuple[str, str, int, float, int]] = []
             zero_load: Dict[str, Dict[str, Allocation]] = {}
-            costs: List[float] = []
             scv_rows: List[float] = []  # per-server cs^2 (negative = use global)
-            rows_append, keys_append, costs_append = rows.append, keys.append, costs.append
+            rows_append, keys_append = rows.append, keys.append
             scv_append = scv_rows.append
 
             for server in chunk_servers:
@@ -489,44 +491,54 @@ class BatchedAllocationSolver:
                 server_name = server.name
                 server_max_batch = server.max_batch_size
                 min_replicas = float(server.min_num_replicas)
+                no_load = arrival == 0 or out_tok == 0
+                if not no_load:
+                    # the row fields that depend on the server alone, formed
+                    # once for all its candidates
+                    K = int(out_tok)
+                    if K == 0 and server_max_batch > 0:
+                        # 0 < out_tokens < 1: create_allocation's analyzer
+                        # rejects the request size before TPS / K is formed
+                        continue
+                    in_tokens, out_tokens = float(int(in_tok)), float(K)
+                    # (K == 0 without a batch override divides by zero in
+                    # the N rule below, as create_allocation does)
+                    total_rate = (
+                        arrival / 60.0 if target_tps == 0 or K == 0 else target_tps / out_tokens
+                    ) * headroom_factor
                 candidates = server.get_candidate_accelerators(accelerators)
                 for acc in candidates.values():
                     info = pair_info(model, acc)
                     if info is None:
                         continue
-                    if arrival == 0 or out_tok == 0:
+                    if no_load:
                         perf = model.get_perf_data(acc.name)
                         alloc = _zero_load_allocation(server, model, acc, perf)
                         zero_load.setdefault(server_name, {})[acc.name] = alloc
                         continue
-                    alpha, beta, gamma, delta, perf_max_batch, at_tokens, cost_per_rep = info
-                    K = int(out_tok)
+                    alpha, beta, gamma, delta, perf_max_batch, at_tokens, unit_cost, instances = info
                     N = server_max_batch if server_max_batch > 0 else max(perf_max_batch * at_tokens // K, 1)
-                    total_rate = (
-                        arrival / 60.0 if target_tps == 0 else target_tps / float(K)
-                    ) * headroom_factor
                     rows_append(
-                        (alpha, beta, gamma, delta, float(int(in_tok)), float(K), float(N),
+                        (alpha, beta, gamma, delta, in_tokens, out_tokens, float(N),
                          target_ttft, target_itl, target_tps, total_rate, min_replicas)
                     )
-                    keys_append((server_name, acc.name, N))
-                    costs_append(cost_per_rep)
+                    keys_append((server_name, acc.name, N, unit_cost, instances))
                     if track_scv:
                         scv_append(getattr(server, "service_scv", -1.0))
 
             ticket = None
             if rows:
                 ticket = dispatch.submit(np.array(rows, dtype=np.float64), scv_rows)
-            return ticket, keys, costs, zero_load
+            return ticket, keys, zero_load
 
-        def apply_results(ticket, keys, costs, zero_load):
+        def apply_results(ticket, keys, zero_load):
             """Collect one slice and turn its results into Allocations."""
             if ticket is not None:
                 # plain floats beat numpy scalar access
                 results_list = dispatch.collect(ticket).tolist()
             else:
                 results_list = []
-            for (server_name, acc_name, N), res, cost_per_replica in zip(keys, results_list, costs):
+            for (server_name, acc_name, N, unit_cost, instances), res in zip(keys, results_list):
                 if res[R_FEASIBLE] != 1.0:
                     continue
                 server = servers[server_name]
@@ -535,7 +547,9 @@ class BatchedAllocationSolver:
                     accelerator=acc_name,
                     num_replicas=num_replicas,
                     batch_size=N,
-                    cost=cost_per_replica * num_replicas,
+                    # create_allocation's association: the product of the
+                    # two integers is exact, so equal prices stay equal
+                    cost=unit_cost * (instances * num_replicas),
                     itl=res[R_ITL],
                     ttft=res[R_TTFT],
                     rho=res[R_RHO],
