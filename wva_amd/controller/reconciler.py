@@ -147,7 +147,15 @@ class VariantAutoscalingReconciler:
             row = np.array(
                 [[10.0, 0.1, 20.0, 0.01, 128, 64, 8, 500.0, 24.0, 0.0, 1.0, 1.0]]
             )
-            solve_problems(row, self.analyzer_device if self.batched_analyzer else None)
+            device = self.analyzer_device if self.batched_analyzer else None
+            from ..analyzer.mg1 import configured_scv
+
+            scv = configured_scv()
+            if scv != 1.0:
+                # mg1 mode sizes with an explicit cs^2 vector: prime that path
+                solve_problems(row, device, scv=scv)
+            else:
+                solve_problems(row, device)
         except Exception as e:  # pragma: no cover - never fatal
             log.debug("analyzer warmup skipped", error=str(e))
 

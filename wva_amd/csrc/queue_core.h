@@ -40,6 +40,23 @@ constexpr int kMaxQueueToBatchRatio = 10;    // K = (1 + ratio) * N
 // methods reject it.  in_tokens, out_tokens, N and min_replicas are
 // truncated toward zero (Python's int()), so a replica count is always
 // integral.
+//
+// M/G/1 correction (per-row service-time cs^2):
+//   - a sizing row may carry a service-time cs^2, scv;
+//   - wait_scale = (1 + scv) / 2;
+//   - TTFT is wait * wait_scale + prefill(eff_conc) wherever it is
+//     evaluated: in the bisection and in the final R_TTFT;
+//   - nothing else changes; the wait >= 0 clamp stays before the scaling;
+//   - scv must be finite and >= 0; any other value gives the all-zero
+//     result row in every implementation (QueueAnalyzer rejects scv < 0,
+//     the native guard also rejects NaN and inf);
+//   - the -1 sentinel means "use the fleet value"; it is resolved on the
+//     host, and a kernel never sees it;
+//   - the 12-column problem layout and the 6-column result layout do not
+//     change: scv travels as a separate optional float64 vector of length B
+//     (absent means 1.0 for every row, the Markovian model).
+// No vector, or a vector of all 1.0, gives results bit-identical to the
+// Markovian ones (x * 1.0 is exact, and fma(x, 1.0, y) rounds x + y).
 enum ProblemField {
   P_ALPHA = 0,    // decode base (ms), >= 0
   P_BETA,         // decode slope (ms per batch unit), >= 0
@@ -73,6 +90,7 @@ struct Parms {
   int out_tokens;
   int max_batch;   // N
   int num_decode;  // out_tokens-1, or 1 for decode-only single-token
+  double wait_scale;  // (1 + scv) / 2; 1.0 is the Markovian model
 };
 
 // largest N whose chain length (1 + ratio) * N still fits an int
@@ -82,8 +100,10 @@ constexpr int kMaxBatchLimit = 2147483647 / (1 + kMaxQueueToBatchRatio);
 // test is written to hold only for a proper value.  Branch-free (& rather
 // than && or early returns): the kernels run this before anything else,
 // and nothing in it should make one load wait for another's compare.
-WVA_HD bool row_valid(const double *pr) {
-  bool ok = true;
+// scv is the row's service-time cs^2 (1.0 when the launch carries none):
+// finite and >= 0, so the -1 sentinel never passes.
+WVA_HD bool row_valid(const double *pr, double scv = 1.0) {
+  bool ok = (scv >= 0.0) & (scv <= 1.7976931348623157e308);
   for (int f = 0; f < PROBLEM_FIELDS; ++f) {
     ok &= fabs(pr[f]) <= 1.7976931348623157e308;  // fails NaN, +-inf
   }
@@ -97,7 +117,7 @@ WVA_HD bool row_valid(const double *pr) {
 }
 
 // Model constants of a VALID row (the int casts are undefined otherwise).
-WVA_HD Parms parms_from_problem(const double *pr) {
+WVA_HD Parms parms_from_problem(const double *pr, double scv = 1.0) {
   Parms p;
   p.alpha = pr[P_ALPHA];
   p.beta = pr[P_BETA];
@@ -108,11 +128,13 @@ WVA_HD Parms parms_from_problem(const double *pr) {
   p.max_batch = (int)pr[P_MAX_BATCH];
   p.num_decode = p.out_tokens - 1;
   if (p.in_tokens == 0.0 && p.out_tokens == 1) p.num_decode = 1;
+  p.wait_scale = (1.0 + scv) / 2.0;
   return p;
 }
 
 // Chain length K = 11 * N of a row; 0 for an invalid row, which needs no
-// table at all.
+// table at all.  It sizes tables from the 12 columns alone: a row rejected
+// for its scv only reserves a table nobody fills.
 WVA_HD int row_chain_length(const double *pr) {
   return row_valid(pr) ? (int)pr[P_MAX_BATCH] * (1 + kMaxQueueToBatchRatio) : 0;
 }
@@ -326,7 +348,7 @@ WVA_HD Stats eval_model(const Parms &p, const double *cum, int K, double lam) {
 
 WVA_HD double eval_ttft_of(const Parms &p, const Stats &st) {
   double effc = effective_concurrency(p, st.serv);
-  return st.wait + prefill_time(p, effc);
+  return st.wait * p.wait_scale + prefill_time(p, effc);
 }
 
 WVA_HD double eval_itl_of(const Parms &p, const Stats &st) {

@@ -63,11 +63,13 @@ inline int binary_search_host(double x_min, double x_max, double y_target, F eva
 
 // Scalar solve of one problem (CPU path).  cum must hold
 // row_chain_length(pr) doubles; a row that breaks the contract of
-// queue_core.h yields the all-zero row and touches no table.
-inline void solve_one(const double *pr, double *out, double *cum) {
+// queue_core.h yields the all-zero row and touches no table.  scv is the
+// row's service-time cs^2 (1.0: Markovian); it only enters through
+// Parms::wait_scale in eval_ttft_of.
+inline void solve_one(const double *pr, double *out, double *cum, double scv = 1.0) {
   for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
-  if (!row_valid(pr)) return;
-  Parms p = parms_from_problem(pr);
+  if (!row_valid(pr, scv)) return;
+  Parms p = parms_from_problem(pr, scv);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   double acc = 0.0;

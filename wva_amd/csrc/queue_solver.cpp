@@ -29,18 +29,35 @@
 // launched); otherwise the hipError_t of the failed launch
 extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
                                 int max_k, void *stream);
+// the same with one service-time cs^2 per row (device pointer; nullptr is
+// the Markovian launch above)
+extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, double *out,
+                                    int n_problems, int max_k, void *stream);
 
 // submit/collect on numpy arrays: the asynchronous, copy-light way into
 // the same launcher (what wva_amd/ops/batched.py uses on the GPU)
 #include "sizing_dispatch.h"
 #endif
 
-static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hint = -1) {
+// scv: optional per-row service-time cs^2 (queue_core.h, M/G/1 correction):
+// float64, contiguous, [B], on the device of problems.  Absent is the
+// Markovian model, bit-identical to a vector of ones.
+static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hint = -1,
+                                       c10::optional<torch::Tensor> scv = c10::nullopt) {
   TORCH_CHECK(problems.dim() == 2 && problems.size(1) == wva::PROBLEM_FIELDS,
               "problems must be [B, ", (int)wva::PROBLEM_FIELDS, "]");
   TORCH_CHECK(problems.scalar_type() == torch::kFloat64, "problems must be float64");
   problems = problems.contiguous();
   const int64_t B = problems.size(0);
+  const double *scv_ptr = nullptr;
+  if (scv.has_value()) {
+    const torch::Tensor &v = *scv;
+    TORCH_CHECK(v.scalar_type() == torch::kFloat64, "scv must be float64");
+    TORCH_CHECK(v.dim() == 1 && v.size(0) == B, "scv must be [B] = [", B, "]");
+    TORCH_CHECK(v.is_contiguous(), "scv must be contiguous");
+    TORCH_CHECK(v.device() == problems.device(), "scv must be on the device of problems");
+    if (B > 0) scv_ptr = v.data_ptr<double>();
+  }
   // the GPU kernels write all six fields of every row (rejected rows
   // included), so only the CPU path needs a zeroed output
   auto out = problems.is_cuda()
@@ -71,9 +88,9 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
     }
     auto stream = c10::hip::getCurrentHIPStream();
     // the launcher picks the geometry and sizes its LDS before launching
-    const int status = wva_launch_solve(problems.data_ptr<double>(),
-                                        out.data_ptr<double>(), (int)B, max_k,
-                                        (void *)stream.stream());
+    const int status = wva_launch_solve_scv(problems.data_ptr<double>(), scv_ptr,
+                                            out.data_ptr<double>(), (int)B, max_k,
+                                            (void *)stream.stream());
     TORCH_CHECK(status != -1,
                 "max_batch too large for the LDS-resident GPU path (limit ~700, "
                 "chain length ", max_k, "); use the CPU path for these problems");
@@ -97,7 +114,7 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
     std::vector<double> cum((size_t)max_k);
     for (int64_t i = begin; i < end; ++i) {
       wva::solve_one(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
-                     cum.data());
+                     cum.data(), scv_ptr ? scv_ptr[i] : 1.0);
     }
   });
   return out;
@@ -107,15 +124,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "wva_amd native batched queue solver (CPU + gfx950 HIP)";
   m.def("solve_allocations", &solve_allocations,
         "Batched state-dependent M/M/1/K allocation sizing",
-        pybind11::arg("problems"), pybind11::arg("max_k_hint") = -1);
+        pybind11::arg("problems"), pybind11::arg("max_k_hint") = -1,
+        pybind11::arg("scv") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
 #ifdef WVA_WITH_HIP
   m.def("submit", &wva::dispatch::submit,
         "Enqueue upload, sizing kernel and download for a float64 [B, 12] "
-        "numpy array on the private dispatch stream; returns a ticket "
+        "numpy array (and an optional float64 [B] vector of per-row "
+        "service-time cs^2) on the private dispatch stream; returns a ticket "
         "without waiting",
-        pybind11::arg("problems"), pybind11::arg("max_k"));
+        pybind11::arg("problems"), pybind11::arg("max_k"),
+        pybind11::arg("scv") = pybind11::none());
   m.def("collect", &wva::dispatch::collect,
         "Wait (GIL released) for a ticket and return its float64 [B, 6] results",
         pybind11::arg("ticket"));

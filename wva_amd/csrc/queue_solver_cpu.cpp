@@ -9,18 +9,35 @@
 #include <pybind11/pybind11.h>
 
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "queue_host.h"
 
 namespace py = pybind11;
 
+// scv: optional per-row service-time cs^2 (queue_core.h, M/G/1 correction).
+// Unlike problems it is never converted: float64, C-contiguous, [B], or the
+// call raises.  None is the Markovian model, bit-identical to all ones.
 static py::array_t<double> solve_allocations(
-    py::array_t<double, py::array::c_style | py::array::forcecast> problems) {
+    py::array_t<double, py::array::c_style | py::array::forcecast> problems,
+    py::object scv) {
   auto buf = problems.request();
   if (buf.ndim != 2 || buf.shape[1] != (ssize_t)wva::PROBLEM_FIELDS)
     throw std::invalid_argument("problems must be [B, 12] float64");
   const ssize_t B = buf.shape[0];
+  const double *scv_ptr = nullptr;
+  py::array scv_arr;  // keeps the vector alive while the GIL is released
+  if (!scv.is_none()) {
+    if (!py::isinstance<py::array_t<double>>(scv))
+      throw py::type_error("scv must be a float64 array");
+    scv_arr = py::reinterpret_borrow<py::array>(scv);
+    if (scv_arr.ndim() != 1 || scv_arr.shape(0) != B)
+      throw py::value_error("scv must be [B] = [" + std::to_string(B) + "]");
+    if (!(scv_arr.flags() & py::array::c_style))
+      throw py::value_error("scv must be C-contiguous");
+    scv_ptr = (const double *)scv_arr.data();
+  }
   auto out = py::array_t<double>({B, (ssize_t)wva::RESULT_FIELDS});
   auto out_buf = out.request();
   const double *pr = (const double *)buf.ptr;
@@ -42,7 +59,7 @@ static py::array_t<double> solve_allocations(
 #pragma omp for schedule(dynamic, 8)
       for (ssize_t i = 0; i < B; ++i) {
         wva::solve_one(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
-                       cum.data());
+                       cum.data(), scv_ptr ? scv_ptr[i] : 1.0);
       }
     }
   }
@@ -52,7 +69,8 @@ static py::array_t<double> solve_allocations(
 PYBIND11_MODULE(_queue_native_cpu, m) {
   m.doc() = "wva_amd torch-free batched queue solver (CPU/OpenMP)";
   m.def("solve_allocations", &solve_allocations,
-        "Batched state-dependent M/M/1/K allocation sizing", py::arg("problems"));
+        "Batched state-dependent M/M/1/K allocation sizing", py::arg("problems"),
+        py::arg("scv") = py::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
 }

@@ -26,6 +26,9 @@
 //     breaks the contract of queue_core.h, or whose chain exceeds the
 //     max_k this launch reserved, gets the all-zero row before LDS is
 //     touched;
+//   - a launch may carry one service-time cs^2 per row (M/G/1 correction,
+//     queue_core.h): it scales the wait inside eval_ttft_of and nowhere
+//     else, so every body and both searches pick it up through Parms;
 //   - LDS budget: (max_k + THREADS + 64) doubles <= 64 KiB for N <= ~700;
 //     the launcher checks it for the geometry it picked before launching
 //     and the binding raises when it does not fit (batched.py routes
@@ -310,13 +313,21 @@ __device__ int wg_binary_search(double x_min, double x_max, double y_target, F e
   return 0;
 }
 
+// The row's cs^2: the launch's optional vector, indexed by the workgroup's
+// row; a launch without one is Markovian (1.0), so stale bytes behind a
+// reused buffer are never read.
+__device__ inline double row_scv(const double *scv, int pid) {
+  return scv != nullptr ? scv[pid] : 1.0;
+}
+
 // Row guard shared by the three bodies, taken before anything touches
-// LDS: a row that breaks the contract of queue_core.h (row_valid), or whose
-// chain does not fit the max_k doubles this launch reserved for cum, gets
-// the all-zero result row.  Every thread of the workgroup reads the same
-// row, so the early return is uniform and precedes the first barrier.
-__device__ inline bool row_rejected(const double *pr, double *res, int max_k) {
-  const bool ok = row_valid(pr) && row_chain_length(pr) <= max_k;
+// LDS: a row that breaks the contract of queue_core.h (row_valid, which
+// also wants the row's cs^2 finite and >= 0), or whose chain does not fit
+// the max_k doubles this launch reserved for cum, gets the all-zero result
+// row.  Every thread of the workgroup reads the same row, so the early
+// return is uniform and precedes the first barrier.
+__device__ inline bool row_rejected(const double *pr, double scv, double *res, int max_k) {
+  const bool ok = row_valid(pr, scv) & (row_chain_length(pr) <= max_k);
   if (!ok && threadIdx.x < RESULT_FIELDS) res[threadIdx.x] = 0.0;
   return !ok;
 }
@@ -342,7 +353,8 @@ __device__ void build_cum(const Parms &p, int K, double *cum, double *totals) {
 }
 
 template <int THREADS>
-__device__ void solve_body(const double *__restrict__ prob, double *__restrict__ out,
+__device__ void solve_body(const double *__restrict__ prob,
+                           const double *__restrict__ scv, double *__restrict__ out,
                            int n_problems, int max_k) {
   const int pid = blockIdx.x;
   if (pid >= n_problems) return;
@@ -350,8 +362,9 @@ __device__ void solve_body(const double *__restrict__ prob, double *__restrict__
   double *res = out + (size_t)pid * RESULT_FIELDS;
   const int tid = threadIdx.x;
 
-  if (row_rejected(pr, res, max_k)) return;
-  const Parms p = parms_from_problem(pr);
+  const double cs2 = row_scv(scv, pid);
+  if (row_rejected(pr, cs2, res, max_k)) return;
+  const Parms p = parms_from_problem(pr, cs2);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
@@ -422,8 +435,9 @@ __device__ void solve_body(const double *__restrict__ prob, double *__restrict__
 // returns infeasible without touching ITL — here both run, but the
 // combined feasibility check and the zeroed result row give the same
 // observable output.
-__device__ void solve_body_dual(const double *__restrict__ prob, double *__restrict__ out,
-                                int n_problems, int max_k) {
+__device__ void solve_body_dual(const double *__restrict__ prob,
+                                const double *__restrict__ scv,
+                                double *__restrict__ out, int n_problems, int max_k) {
   constexpr int THREADS = 128;
   const int pid = blockIdx.x;
   if (pid >= n_problems) return;
@@ -432,8 +446,9 @@ __device__ void solve_body_dual(const double *__restrict__ prob, double *__restr
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
 
-  if (row_rejected(pr, res, max_k)) return;
-  const Parms p = parms_from_problem(pr);
+  const double cs2 = row_scv(scv, pid);
+  if (row_rejected(pr, cs2, res, max_k)) return;
+  const Parms p = parms_from_problem(pr, cs2);
   const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
@@ -681,8 +696,10 @@ __device__ int spec_binary_search(double x_min, double x_max, double y_target,
 //   [14..20] group-1 y slots      [21..27] group-1 flags
 //   [28..31] results: lam0, ind0, lam1, ind1
 //   [32..33] done flags per group
+//   [40..47] depth 3 only: the row's Parms (see below)
 template <int D>
 __device__ void solve_body_spec(const double *__restrict__ prob,
+                                const double *__restrict__ scv,
                                 double *__restrict__ out, int n_problems,
                                 int max_k) {
   constexpr int SW = (1 << D) - 1;
@@ -697,17 +714,31 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
   const int sub = wave % SW;
   const int lane = tid & 63;
 
-  if (row_rejected(pr, res, max_k)) return;
-  const Parms p = parms_from_problem(pr);
-  const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
+  const double cs2 = row_scv(scv, pid);
+  if (row_rejected(pr, cs2, res, max_k)) return;
+  const Parms p0 = parms_from_problem(pr, cs2);
+  const int K = p0.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
   double *cum = smem;
   double *totals = smem + max_k;
   double *mail = totals + THREADS;
   if (tid < 34) mail[tid] = 0.0;
+  // The 896-thread geometry has 128 vector registers per lane and spills:
+  // there the searches read the row's constants from LDS (8 of the 64
+  // slack doubles, published by the scan's closing barrier) instead of
+  // holding all of them, wait_scale included, in registers.  Same values,
+  // same arithmetic.
+  static_assert(sizeof(Parms) <= 8 * sizeof(double), "Parms outgrew its LDS slot");
+  const Parms *pp = &p0;
+  if constexpr (D == 3) {
+    Parms *shared_parms = reinterpret_cast<Parms *>(mail + 40);
+    if (tid == 0) *shared_parms = p0;
+    pp = shared_parms;
+  }
 
-  build_cum<THREADS>(p, K, cum, totals);  // ends with __syncthreads()
+  build_cum<THREADS>(p0, K, cum, totals);  // ends with __syncthreads()
+  const Parms &p = *pp;
 
   const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
   const double lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
@@ -778,33 +809,33 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
 }
 
 extern "C" __global__ void __launch_bounds__(384) wva_solve_kernel_384(
-    const double *__restrict__ prob, double *__restrict__ out, int n_problems,
-    int max_k) {
-  solve_body_spec<2>(prob, out, n_problems, max_k);
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    double *__restrict__ out, int n_problems, int max_k) {
+  solve_body_spec<2>(prob, scv, out, n_problems, max_k);
 }
 
 extern "C" __global__ void __launch_bounds__(896) wva_solve_kernel_896(
-    const double *__restrict__ prob, double *__restrict__ out, int n_problems,
-    int max_k) {
-  solve_body_spec<3>(prob, out, n_problems, max_k);
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    double *__restrict__ out, int n_problems, int max_k) {
+  solve_body_spec<3>(prob, scv, out, n_problems, max_k);
 }
 
 extern "C" __global__ void __launch_bounds__(256) wva_solve_kernel_256(
-    const double *__restrict__ prob, double *__restrict__ out, int n_problems,
-    int max_k) {
-  solve_body<256>(prob, out, n_problems, max_k);
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    double *__restrict__ out, int n_problems, int max_k) {
+  solve_body<256>(prob, scv, out, n_problems, max_k);
 }
 
 extern "C" __global__ void __launch_bounds__(64) wva_solve_kernel_64(
-    const double *__restrict__ prob, double *__restrict__ out, int n_problems,
-    int max_k) {
-  solve_body<64>(prob, out, n_problems, max_k);
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    double *__restrict__ out, int n_problems, int max_k) {
+  solve_body<64>(prob, scv, out, n_problems, max_k);
 }
 
 extern "C" __global__ void __launch_bounds__(128) wva_solve_kernel_128(
-    const double *__restrict__ prob, double *__restrict__ out, int n_problems,
-    int max_k) {
-  solve_body_dual(prob, out, n_problems, max_k);
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    double *__restrict__ out, int n_problems, int max_k) {
+  solve_body_dual(prob, scv, out, n_problems, max_k);
 }
 
 }  // namespace wva
@@ -815,8 +846,11 @@ extern "C" __global__ void __launch_bounds__(128) wva_solve_kernel_128(
 // Returns 0 on success, -1 when the selected geometry's LDS footprint
 // (cum[max_k] + totals[threads] + 64 slack doubles) exceeds 64 KiB — decided
 // BEFORE anything is launched — or the hipError_t of a failed launch.
-extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
-                                int max_k, void *stream) {
+// scv is the optional device vector of per-row service-time cs^2 (n_problems
+// doubles); nullptr launches the Markovian model.  It changes neither the
+// geometry pick nor the LDS size.
+extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, double *out,
+                                    int n_problems, int max_k, void *stream) {
   // Geometry auto-selects on state-chain length (measured:
   // profiles/r01_queue_solver.md, profiles/r01_kernel_sweep.json).  The
   // 2-wave dual kernel overlaps the TTFT and ITL bisections and is the
@@ -860,19 +894,24 @@ extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
   const size_t smem = (size_t)(max_k + threads + 64) * sizeof(double);
   if (threads == 64) {
     hipLaunchKernelGGL(wva::wva_solve_kernel_64, dim3(n_problems), dim3(64), smem,
-                       (hipStream_t)stream, prob, out, n_problems, max_k);
+                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
   } else if (threads == 128) {
     hipLaunchKernelGGL(wva::wva_solve_kernel_128, dim3(n_problems), dim3(128), smem,
-                       (hipStream_t)stream, prob, out, n_problems, max_k);
+                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
   } else if (threads == 384) {
     hipLaunchKernelGGL(wva::wva_solve_kernel_384, dim3(n_problems), dim3(384), smem,
-                       (hipStream_t)stream, prob, out, n_problems, max_k);
+                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
   } else if (threads == 896) {
     hipLaunchKernelGGL(wva::wva_solve_kernel_896, dim3(n_problems), dim3(896), smem,
-                       (hipStream_t)stream, prob, out, n_problems, max_k);
+                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
   } else {
     hipLaunchKernelGGL(wva::wva_solve_kernel_256, dim3(n_problems), dim3(256), smem,
-                       (hipStream_t)stream, prob, out, n_problems, max_k);
+                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
+                                int max_k, void *stream) {
+  return wva_launch_solve_scv(prob, nullptr, out, n_problems, max_k, stream);
 }

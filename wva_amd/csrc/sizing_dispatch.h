@@ -1,6 +1,7 @@
 // Asynchronous, copy-light dispatch of the gfx950 sizing kernel.
 //
-// submit() stages a [B, 12] float64 problem matrix in pinned host memory,
+// submit() stages a [B, 12] float64 problem matrix (and an optional [B]
+// cs^2 vector) in pinned host memory,
 // enqueues upload -> kernel -> download on one private stream, records an
 // event and returns a ticket without waiting; collect() waits for that
 // event (GIL released) and hands the [B, 6] results back as a fresh numpy
@@ -15,6 +16,13 @@
 // body writes all six fields of every row it owns (row_rejected zeroes a
 // rejected row; the bodies zero the row before the searches and thread 0
 // writes the six results at the end), so no memset precedes the launch.
+//
+// A submit may carry one service-time cs^2 per row (queue_core.h, M/G/1
+// correction).  The vector rides in the slot's input buffers, right behind
+// the B rows, so the one upload copy moves both and nothing is created per
+// call.  A submit without one uploads the rows alone and launches with a
+// null vector: whatever an earlier submit left behind the rows of a reused
+// slot is never read.
 //
 // Buffers live in a pool of slots, each with pinned in/out, device in/out
 // and an event created with hipEventDisableTiming.  Slots are grow-only;
@@ -47,8 +55,8 @@
 
 #include "queue_core.h"
 
-extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
-                                int max_k, void *stream);
+extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, double *out,
+                                    int n_problems, int max_k, void *stream);
 
 namespace wva {
 namespace dispatch {
@@ -81,7 +89,7 @@ struct DeviceGuard {
 enum class SlotState { kFree, kInFlight, kCollecting };
 
 struct Slot {
-  double *h_in = nullptr;   // pinned, cap_rows * PROBLEM_FIELDS
+  double *h_in = nullptr;   // pinned, cap_rows * (PROBLEM_FIELDS + 1): rows, then scv
   double *h_out = nullptr;  // pinned, cap_rows * RESULT_FIELDS
   double *d_in = nullptr;
   double *d_out = nullptr;
@@ -118,7 +126,8 @@ inline void grow_slot(Slot &s, int64_t rows) {
   s.h_in = s.h_out = s.d_in = s.d_out = nullptr;
   s.cap_rows = 0;
   const int64_t cap = (rows + 255) / 256 * 256;
-  const size_t in_bytes = (size_t)cap * PROBLEM_FIELDS * sizeof(double);
+  // one more double per row: the optional cs^2 vector behind the rows
+  const size_t in_bytes = (size_t)cap * (PROBLEM_FIELDS + 1) * sizeof(double);
   const size_t out_bytes = (size_t)cap * RESULT_FIELDS * sizeof(double);
   hip_check(hipHostMalloc((void **)&s.h_in, in_bytes, hipHostMallocDefault),
             "hipHostMalloc");
@@ -129,7 +138,7 @@ inline void grow_slot(Slot &s, int64_t rows) {
   s.cap_rows = cap;
 }
 
-inline int64_t submit(py::array problems, int64_t max_k) {
+inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::none()) {
   if (!py::isinstance<py::array_t<double>>(problems)) {
     throw py::type_error("problems must be a float64 array");
   }
@@ -142,6 +151,20 @@ inline int64_t submit(py::array problems, int64_t max_k) {
   }
   const int64_t B = problems.shape(0);
   if (B > INT_MAX) throw py::value_error("too many problems for one launch");
+  const double *scv_src = nullptr;
+  if (!scv.is_none()) {
+    if (!py::isinstance<py::array_t<double>>(scv)) {
+      throw py::type_error("scv must be a float64 array");
+    }
+    py::array v = py::reinterpret_borrow<py::array>(scv);
+    if (v.ndim() != 1 || v.shape(0) != B) {
+      throw py::value_error("scv must be [B] = [" + std::to_string(B) + "]");
+    }
+    if (!(v.flags() & py::array::c_style)) {
+      throw py::value_error("scv must be C-contiguous");
+    }
+    scv_src = (const double *)v.data();  // the caller's scv outlives this call
+  }
 
   Pool &P = pool();
   std::lock_guard<std::mutex> lock(P.mu);
@@ -180,15 +203,20 @@ inline int64_t submit(py::array problems, int64_t max_k) {
   // it reusable
   grow_slot(*slot, B);
 
-  const size_t in_bytes = (size_t)B * PROBLEM_FIELDS * sizeof(double);
+  const size_t row_doubles = (size_t)B * PROBLEM_FIELDS;
+  const size_t in_doubles = row_doubles + (scv_src != nullptr ? (size_t)B : 0);
   const size_t out_bytes = (size_t)B * RESULT_FIELDS * sizeof(double);
-  std::memcpy(slot->h_in, problems.data(), in_bytes);
-  hip_check(hipMemcpyAsync(slot->d_in, slot->h_in, in_bytes,
+  std::memcpy(slot->h_in, problems.data(), row_doubles * sizeof(double));
+  if (scv_src != nullptr) {
+    std::memcpy(slot->h_in + row_doubles, scv_src, (size_t)B * sizeof(double));
+  }
+  hip_check(hipMemcpyAsync(slot->d_in, slot->h_in, in_doubles * sizeof(double),
                            hipMemcpyHostToDevice, P.stream),
             "hipMemcpyAsync (upload)");
   const int k = max_k > INT_MAX ? INT_MAX : (max_k < 0 ? 0 : (int)max_k);
-  const int status =
-      wva_launch_solve(slot->d_in, slot->d_out, (int)B, k, (void *)P.stream);
+  const double *d_scv = scv_src != nullptr ? slot->d_in + row_doubles : nullptr;
+  const int status = wva_launch_solve_scv(slot->d_in, d_scv, slot->d_out, (int)B, k,
+                                          (void *)P.stream);
   if (status != 0) {
     // nothing was launched; let the upload finish before the slot's pinned
     // buffer can be overwritten by the next submit

@@ -6,8 +6,12 @@ allocation.go:27-163).  Here the analyze phase is *batched*: all pairs of
 the fleet are packed into one [B, 12] float64 matrix and solved either by
 the native extension (the torch-free C++/OpenMP binding on CPU, or the
 gfx950 HIP kernel — one workgroup per pair) or by the pure-Python
-analyzer fallback; mg1 mode routes through the scalar analyzer with
-per-server cs^2 support.  On the GPU the matrix travels through the native
+analyzer fallback.  M/G/1-corrected sizing (a per-row service-time cs^2,
+below) runs on the same native paths: ``BatchedAllocationSolver`` resolves
+each server's cs^2 and hands the vector to ``solve_problems(..., scv=...)``.
+Only a bare ``solve_problems(problems)`` under ``WVA_ANALYZER=mg1`` — no
+explicit ``scv`` — still routes through the scalar Python analyzer with the
+environment's fleet value.  On the GPU the matrix travels through the native
 submit/collect dispatch (csrc/sizing_dispatch.h), and
 ``BatchedAllocationSolver`` may cut the fleet into chunks so that its own
 per-row host work overlaps the launches (docs/design/native-queue-solver.md).
@@ -25,6 +29,24 @@ contract (``row_valid`` there, ``valid_rows`` here).  A row is valid iff
 An invalid row yields the all-zero result row in every implementation, as
 the analyzer's ``check()`` methods reject it.  in_tokens, out_tokens, N and
 min_replicas are truncated toward zero, so replica counts are integral.
+
+M/G/1 correction (per-row service-time cs^2; ``valid_scv`` here):
+
+- a sizing row may carry a service-time cs^2, ``scv``;
+- ``wait_scale = (1 + scv) / 2``;
+- TTFT is ``wait * wait_scale + prefill(eff_conc)`` wherever it is
+  evaluated: in the bisection and in the final ``R_TTFT``;
+- nothing else changes; the ``wait >= 0`` clamp stays before the scaling;
+- ``scv`` must be finite and ``>= 0``; any other value gives the all-zero
+  result row in every implementation (``QueueAnalyzer`` rejects ``scv < 0``,
+  the native guard also rejects NaN and inf);
+- the ``-1`` sentinel means "use the fleet value"; it is resolved on the
+  host, and a kernel never sees it;
+- the 12-column problem layout and the 6-column result layout do not
+  change: ``scv`` travels as a separate optional float64 vector of length B.
+
+No vector, or a vector of all 1.0, gives results bit-identical to the
+Markovian ones on every path.
 """
 
 from __future__ import annotations
@@ -81,9 +103,33 @@ def valid_rows(problems: np.ndarray) -> np.ndarray:
         ok &= (p[:, P_TARGET_TTFT : P_TARGET_TPS + 1] >= 0).all(axis=1)
     return ok
 
+
+def valid_scv(scv: np.ndarray) -> np.ndarray:
+    """Boolean mask of the service-time cs^2 values a row may carry: finite
+    and >= 0 (the ``scv`` part of ``row_valid`` in csrc/queue_core.h).  The
+    ``-1`` sentinel fails it: it must be resolved before a solver sees it."""
+    with np.errstate(invalid="ignore"):
+        return np.isfinite(scv) & (scv >= 0)
+
+
+def _scv_vector(scv, n_rows: int) -> np.ndarray:
+    """An explicit ``scv`` — a scalar for the whole batch or a float64
+    ``[B]`` array — as the C-contiguous float64 ``[B]`` vector the native
+    bindings take.  An array of another dtype or shape raises, as the
+    bindings do."""
+    if isinstance(scv, np.ndarray) and scv.ndim > 0:
+        if scv.dtype != np.float64:
+            raise TypeError(f"scv must be float64, got {scv.dtype}")
+        if scv.shape != (n_rows,):
+            raise ValueError(f"scv must be a scalar or [B] = [{n_rows}], got {scv.shape}")
+        return np.ascontiguousarray(scv)
+    return np.full(n_rows, float(scv), dtype=np.float64)
+
+
 # hipGraph dispatch cache: repeated fleet solves of the same shape replay
-# a captured graph instead of re-launching.  Keyed by (B, max_k); replays
-# copy fresh problem data into the captured input buffer.  Opt-in via
+# a captured graph instead of re-launching.  Keyed by (B, max_k, whether the
+# launch carries a cs^2 vector); replays copy fresh problem data (and the
+# fresh cs^2 vector) into the captured input buffers.  Opt-in via
 # WVA_GPU_GRAPH=1: the fleet solve is ONE kernel, so launch overhead is
 # ~1% of the dispatch and replay measured no win (0.96 vs 0.94 ms
 # headline cycle) — the path exists for launch-bound configurations
@@ -112,8 +158,9 @@ def _on_device(device):
     return torch.cuda.device(torch.device(device))
 
 
-def _graph_solve(native, problems_t, max_k):
-    """Solve via a cached hipGraph; None -> caller uses plain dispatch."""
+def _graph_solve(native, problems_t, max_k, scv_t=None):
+    """Solve via a cached hipGraph; None -> caller uses plain dispatch.
+    ``scv_t`` is the optional device vector of per-row cs^2."""
     global _graph_lock, _graph_disabled
     import threading
 
@@ -123,7 +170,7 @@ def _graph_solve(native, problems_t, max_k):
 
     if _graph_lock is None:
         _graph_lock = threading.Lock()
-    key = (problems_t.shape[0], max_k)
+    key = (problems_t.shape[0], max_k, scv_t is not None)
     with _graph_lock:
         entry = _graph_cache.get(key)
         try:
@@ -133,22 +180,25 @@ def _graph_solve(native, problems_t, max_k):
                     # shapes churn; oldest capture goes first
                     _graph_cache.pop(next(iter(_graph_cache)))
                 static_in = problems_t.clone()
+                static_scv = scv_t.clone() if scv_t is not None else None
                 # warm up on a side stream (capture requires a clean stream)
                 side = torch.cuda.Stream()
                 side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side):
-                    native.solve_allocations(static_in, max_k)
+                    native.solve_allocations(static_in, max_k, static_scv)
                 torch.cuda.current_stream().wait_stream(side)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    static_out = native.solve_allocations(static_in, max_k)
-                _graph_cache[key] = (graph, static_in, static_out)
+                    static_out = native.solve_allocations(static_in, max_k, static_scv)
+                _graph_cache[key] = (graph, static_in, static_scv, static_out)
                 # capture only RECORDS the work — replay to actually run
                 # it for this call's data
                 graph.replay()
                 return static_out.cpu().numpy()
-            graph, static_in, static_out = entry
+            graph, static_in, static_scv, static_out = entry
             static_in.copy_(problems_t)
+            if static_scv is not None:
+                static_scv.copy_(scv_t)
             graph.replay()
             return static_out.cpu().numpy()
         except Exception as e:  # pragma: no cover - depends on ROCm graph support
@@ -165,10 +215,11 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
     """Reference-semantics scalar fallback via the Python analyzer.
 
     ``scv`` is the service-time cs^2 — a scalar for the whole batch or a
-    per-row array (mg1 auto mode derives one per server)."""
-    scv_arr = np.broadcast_to(np.asarray(scv, dtype=np.float64), (problems.shape[0],))
+    per-row float64 array (mg1 auto mode derives one per server); a row
+    whose cs^2 fails ``valid_scv`` yields the all-zero row."""
+    scv_arr = _scv_vector(scv, problems.shape[0])
     out = np.zeros((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
-    valid = valid_rows(problems)
+    valid = valid_rows(problems) & valid_scv(scv_arr)
     for i, row in enumerate(problems):
         if not valid[i]:
             continue  # all-zero row; also keeps int() off NaN and inf
@@ -214,29 +265,42 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
     return out
 
 
-def solve_problems(problems: np.ndarray, device: Optional[str] = None) -> np.ndarray:
+def solve_problems(
+    problems: np.ndarray, device: Optional[str] = None, scv=None
+) -> np.ndarray:
     """Solve a [B, 12] problem matrix -> [B, 6] results.
 
     device: None for automatic (native CPU if built, else Python), "cpu" to
     force the native/Python CPU path, or a torch device string like "cuda"
     to run the gfx950 kernel.
+
+    scv: None, or the service-time cs^2 of the M/G/1 correction (module
+    docstring) — a scalar for the whole batch or a float64 ``[B]`` array.
+    An explicit ``scv`` never reads the environment and runs on the native
+    paths (GPU dispatch, else the torch-free binding, else the torch
+    binding; the Python analyzer only when nothing native is built).
+    ``None`` is the Markovian model, except under ``WVA_ANALYZER=mg1``,
+    where the environment's fleet value goes through the Python analyzer.
     """
     from . import get_native, native_available
 
     problems = np.ascontiguousarray(problems, dtype=np.float64)
     if problems.ndim != 2 or problems.shape[1] != PROBLEM_FIELDS:
         raise ValueError(f"problems must be [B, {PROBLEM_FIELDS}]")
+    scv_arr = None if scv is None else _scv_vector(scv, problems.shape[0])
     if problems.shape[0] == 0:
         return np.zeros((0, RESULT_FIELDS), dtype=np.float64)
 
     from ..analyzer.mg1 import configured_scv
 
-    scv = configured_scv()
-    if scv != 1.0:
+    env_scv = 1.0 if scv_arr is not None else configured_scv()
+    if env_scv != 1.0:
+        scv = env_scv
         # WVA_ANALYZER=mg1: the Allen-Cunneen wait scaling lives in the
         # Python analyzer; the native kernels implement the Markovian
         # contract only, so mg1 mode routes through the scalar path
-        # (opt-in capacity-planning mode, not the hot default)
+        # (opt-in capacity-planning mode, not the hot default); callers
+        # that want the native paths pass the cs^2 explicitly
         global _mg1_warned
         if not _mg1_warned:
             _mg1_warned = True
@@ -266,21 +330,28 @@ def solve_problems(problems: np.ndarray, device: Optional[str] = None) -> np.nda
             # LDS-resident limit: solve oversized problems on CPU
             big = batch_limits > GPU_MAX_BATCH_LIMIT
             out = np.empty((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
-            out[~big] = solve_problems(problems[~big], device=device)
-            out[big] = solve_problems(problems[big], device="cpu")
+            if scv_arr is None:
+                out[~big] = solve_problems(problems[~big], device=device)
+                out[big] = solve_problems(problems[big], device="cpu")
+            else:  # each part takes the cs^2 of its own rows
+                out[~big] = solve_problems(problems[~big], device=device, scv=scv_arr[~big])
+                out[big] = solve_problems(problems[big], device="cpu", scv=scv_arr[big])
             return out
         # chain length computed host-side (also feeds hipGraph capture,
         # where the binding's device-sync fallback is illegal)
         max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
         if _graph_requested():
             t = torch.from_numpy(problems).to(device)
-            res = _graph_solve(native, t, max_k)
+            scv_t = None if scv_arr is None else torch.from_numpy(scv_arr).to(device)
+            res = _graph_solve(native, t, max_k, scv_t)
             if res is not None:
                 return res
         # lean dispatch (csrc/sizing_dispatch.h): pinned staging, no output
         # fill, no tensors — here as one chunk, submitted and collected
         with _on_device(device):
-            return native.collect(native.submit(problems, max_k))
+            if scv_arr is None:
+                return native.collect(native.submit(problems, max_k))
+            return native.collect(native.submit(problems, max_k, scv_arr))
 
     from . import get_native_cpu, native_cpu_available
 
@@ -290,24 +361,39 @@ def solve_problems(problems: np.ndarray, device: Optional[str] = None) -> np.nda
         # CPU — plain OpenMP beats at::parallel_for's per-call overhead
         # on this workload (profiles/r01_torchfree_cpu.json) — and it is
         # the only native path in the slim controller image.
-        return get_native_cpu().solve_allocations(problems)
+        if scv_arr is None:
+            return get_native_cpu().solve_allocations(problems)
+        return get_native_cpu().solve_allocations(problems, scv_arr)
     if native_available():
         import torch
 
         native = get_native()
-        return native.solve_allocations(torch.from_numpy(problems)).numpy()
+        if scv_arr is None:
+            return native.solve_allocations(torch.from_numpy(problems)).numpy()
+        return native.solve_allocations(
+            torch.from_numpy(problems), -1, torch.from_numpy(scv_arr)
+        ).numpy()
     from . import warn_if_pure_python_fallback
 
     warn_if_pure_python_fallback()
-    return _solve_problems_python(problems)
+    if scv_arr is None:
+        return _solve_problems_python(problems)
+    return _solve_problems_python(problems, scv=scv_arr)
+
+
+def _resolved_scv(scv_rows, global_scv: float) -> np.ndarray:
+    """The rows' cs^2 with the "use the fleet value" sentinel (any negative
+    value) replaced by ``global_scv``: the vector a solver may see."""
+    return np.array([s if s >= 0 else global_scv for s in scv_rows], dtype=np.float64)
 
 
 class SyncDispatch:
     """submit/collect over today's synchronous ``solve_problems``: ``submit``
     solves on the spot and the ticket is the result.  Runs the chunked
-    pipeline on any device, and carries the M/G/1 routing: ``global_scv`` is
-    given when some server may need the corrected analyzer, and ``submit``
-    then decides from the rows' cs^2 values."""
+    pipeline on any device.  ``global_scv`` is given when some server may
+    need the M/G/1 correction: ``submit`` then resolves the rows' cs^2
+    against it and passes the vector on, so the fleet is sized by the same
+    native path as a Markovian one."""
 
     def __init__(self, device: Optional[str], global_scv: Optional[float] = None) -> None:
         self.device = device
@@ -315,13 +401,8 @@ class SyncDispatch:
 
     def submit(self, problems: np.ndarray, scv_rows=None):
         if self.global_scv is not None:
-            scv_arr = np.array(
-                [s if s >= 0 else self.global_scv for s in scv_rows], dtype=np.float64
-            )
-            if (scv_arr != 1.0).any():
-                # M/G/1-corrected sizing (global mg1 mode and/or
-                # per-server measured cs^2): the scalar analyzer path
-                return _solve_problems_python(problems, scv=scv_arr)
+            scv_arr = _resolved_scv(scv_rows, self.global_scv)
+            return solve_problems(problems, self.device, scv=scv_arr)
         return solve_problems(problems, self.device)
 
     def collect(self, ticket) -> np.ndarray:
@@ -332,19 +413,30 @@ class NativeGpuDispatch:
     """submit/collect over the native asynchronous dispatch
     (csrc/sizing_dispatch.h): ``submit`` returns once upload, kernel and
     download are enqueued, ``collect`` waits for them.  A chunk that needs
-    the oversized-N split to the CPU is solved synchronously instead."""
+    the oversized-N split to the CPU is solved synchronously instead.
+    ``global_scv`` is given when some server may need the M/G/1 correction:
+    ``submit`` then resolves the rows' cs^2 against it and the vector travels
+    with the rows, into the synchronous split too."""
 
-    def __init__(self, native, device: str) -> None:
+    def __init__(self, native, device: str, global_scv: Optional[float] = None) -> None:
         self.native = native
         self.device = device
+        self.global_scv = global_scv
 
     def submit(self, problems: np.ndarray, scv_rows=None):
+        scv_arr = None
+        if self.global_scv is not None:
+            scv_arr = _resolved_scv(scv_rows, self.global_scv)
         max_batch = problems[:, P_MAX_BATCH].max()
         if not max_batch <= GPU_MAX_BATCH_LIMIT:  # also a NaN N
-            return None, solve_problems(problems, self.device)
+            if scv_arr is None:
+                return None, solve_problems(problems, self.device)
+            return None, solve_problems(problems, self.device, scv=scv_arr)
         max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
         with _on_device(self.device):
-            return self.native.submit(problems, max_k), None
+            if scv_arr is None:
+                return self.native.submit(problems, max_k), None
+            return self.native.submit(problems, max_k, scv_arr), None
 
     def collect(self, ticket) -> np.ndarray:
         native_ticket, solved = ticket
@@ -377,8 +469,10 @@ class BatchedAllocationSolver:
     solved independently, and the GPU path chunks only while every chunk
     auto-selects the kernel geometry of the whole batch).  ``chunks=None``
     picks DEFAULT_GPU_CHUNKS on the GPU and 1 elsewhere; 1 is a single
-    call.  A fleet in which some server may take the M/G/1-corrected
-    analyzer is solved as one chunk, the routing decided from all its rows.
+    call.  A fleet in which some server may need the M/G/1 correction
+    (``WVA_ANALYZER=mg1`` or a measured ``service_scv``) carries one cs^2 per
+    row through the same dispatch; on the GPU it is chunked like any other
+    fleet, elsewhere it is one chunk.
     """
 
     def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None) -> None:
@@ -393,10 +487,10 @@ class BatchedAllocationSolver:
         from ..analyzer.mg1 import configured_scv
 
         global_scv = configured_scv()
-        if global_scv != 1.0 or any(
+        track_scv = global_scv != 1.0 or any(
             s >= 0 and s != 1.0 for s in [getattr(v, "service_scv", -1.0) for v in servers]
-        ):
-            return SyncDispatch(self.device, global_scv), 1, True
+        )
+        dispatch_scv = global_scv if track_scv else None
         want_gpu = self.device is not None and str(self.device).startswith("cuda")
         if want_gpu and not _graph_requested():
             from . import get_native
@@ -408,7 +502,9 @@ class BatchedAllocationSolver:
             chunks = self.chunks if self.chunks is not None else DEFAULT_GPU_CHUNKS
             if len(servers) * len(system.accelerators) >= _GPU_CHUNKING_ROW_BOUND:
                 chunks = 1
-            return NativeGpuDispatch(native, self.device), chunks, False
+            return NativeGpuDispatch(native, self.device, dispatch_scv), chunks, track_scv
+        if track_scv:
+            return SyncDispatch(self.device, dispatch_scv), 1, True
         return SyncDispatch(self.device), self.chunks or 1, False
 
     def calculate(self, system: System) -> None:
