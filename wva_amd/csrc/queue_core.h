@@ -346,6 +346,108 @@ WVA_HD Stats eval_model(const Parms &p, const double *cum, int K, double lam) {
   return st;
 }
 
+// ---------------------------------------------------------------------------
+// Compact table: N doubles instead of K = 11 * N.
+//
+// For states n >= N-1 the service rate is constant, so with L_N =
+// log(serv_rate(N)) = log_mu(p, N-1)
+//
+//   cum[n] = cum[N-1] + (n - N + 1) * L_N,   n >= N-1,
+//
+// and an evaluation reads the table proper only in the sweep over the N+1
+// pre-batch states and at the mode (which is at most N-1, or K).  Everything
+// past N is closed form: log_p(N+1), log_p(K), and the constant increment
+// d = log(lam) - L_N of the geometric tail, taken directly instead of as the
+// difference of two table entries of magnitude ~K * |L_N|.  This is the same
+// model, not an approximation of it; near saturation it is the more accurate
+// of the two, since d no longer cancels.
+// ---------------------------------------------------------------------------
+
+// cum[n] for any n in [0, K-1], given cum[0..N-1] and L_N
+WVA_HD double cum_at(const double *cum, int N, double log_mu_n, int n) {
+  const int i = n < N ? n : N - 1;  // the only index ever read
+  const double base = cum[i];
+  return n < N ? base : base + (double)(n - N + 1) * log_mu_n;
+}
+
+WVA_HD double log_p_compact(const double *cum, int N, double log_mu_n, double loglam,
+                            int n) {
+  return (n == 0) ? 0.0 : n * loglam - cum_at(cum, N, log_mu_n, n - 1);
+}
+
+// geo_tail with the first term's exponent x_a = log_p(g_start) - m given by
+// the caller (the compact table has no entry to read it from)
+WVA_HD GeoTail geo_tail_at(double x_a, double d, int g_start, int n_hi, int K) {
+  GeoTail t{0.0, 0.0, 0.0, false};
+  const int M = n_hi - g_start;
+  if (M < 8 || fabs(d) * (double)(M + 1) < 0.01) return t;  // loop is fine/safer
+  const double p_a = exp(x_a);
+  const double e1 = expm1(d);
+  const double G0 = expm1((double)(M + 1) * d) / e1;
+  const double r = e1 + 1.0;
+  const double rM = exp((double)M * d);
+  const double G1 =
+      r * (1.0 - (double)(M + 1) * rM + (double)M * rM * r) / (e1 * e1);
+  t.S = p_a * G0;
+  t.Ni = p_a * ((double)g_start * G0 + G1);
+  if (n_hi == K) t.eK = p_a * exp((double)(K - g_start) * d);
+  t.used = true;
+  return t;
+}
+
+// Stats from the reduced state sums (the closing arithmetic of eval_model)
+WVA_HD Stats stats_of_sums(double lam, int num, double S, double Ni, double Snum,
+                           double Ninum, double eK) {
+  Stats st;
+  st.throughput = lam * (1.0 - eK / S);
+  double n_sys = Ni / S;
+  st.n_serv = Ninum / S + (1.0 - Snum / S) * (double)num;
+  if (st.throughput == 0.0) {
+    st.wait = st.serv = 0.0;
+  } else {
+    double resp = n_sys / st.throughput;
+    st.serv = st.n_serv / st.throughput;
+    st.wait = resp - st.serv;
+    if (st.wait < 0.0) st.wait = 0.0;
+  }
+  return st;
+}
+
+// eval_model over the compact table cum[0..N-1] (same inclusive sum), with
+// log_mu_n = log_mu(p, N-1).  No significance window: the sweep covers the
+// N+1 pre-batch states and the queue region (N, K] sums in closed form; only
+// where geo_tail_at declines (|d| * 10N < 0.01, a sliver around lam = mu(N))
+// does the loop run on to K through cum_at.
+WVA_HD Stats eval_model_compact(const Parms &p, const double *cum, double log_mu_n,
+                                double lam) {
+  const int num = p.max_batch;
+  const int K = num * (1 + kMaxQueueToBatchRatio);
+  const double loglam = log(lam);
+  const int n_star = log_mode_state(p, K, lam);  // in [0, N-1], or K
+  double m = log_p_compact(cum, num, log_mu_n, loglam, n_star);
+  if (m < 0.0) m = 0.0;  // logp(0) = 0 participates in the max
+  const int g_start = num + 1;
+  const double d = loglam - log_mu_n;
+  const GeoTail tail = geo_tail_at(
+      log_p_compact(cum, num, log_mu_n, loglam, g_start) - m, d, g_start, K, K);
+  const int loop_hi = tail.used ? num : K;
+  double S = 0.0, Ni = 0.0, Snum = 0.0, Ninum = 0.0, eK = 0.0;
+  for (int n = 0; n <= loop_hi; ++n) {
+    double e = exp(log_p_compact(cum, num, log_mu_n, loglam, n) - m);
+    S += e;
+    Ni += n * e;
+    if (n <= num) {
+      Snum += e;
+      Ninum += n * e;
+    }
+    if (n == K) eK = e;
+  }
+  S += tail.S;
+  Ni += tail.Ni;
+  eK += tail.eK;
+  return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+}
+
 WVA_HD double eval_ttft_of(const Parms &p, const Stats &st) {
   double effc = effective_concurrency(p, st.serv);
   return st.wait * p.wait_scale + prefill_time(p, effc);

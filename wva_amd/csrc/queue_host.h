@@ -123,4 +123,70 @@ inline void solve_one(const double *pr, double *out, double *cum, double scv = 1
   out[R_RHO] = rho;
 }
 
+// solve_one over the compact table (queue_core.h, eval_model_compact): cum
+// must hold trunc(N) doubles for a valid row, and nothing is touched for an
+// invalid one.  Same semantics, same row contract, same result layout.
+inline void solve_one_compact(const double *pr, double *out, double *cum,
+                              double scv = 1.0) {
+  for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
+  if (!row_valid(pr, scv)) return;
+  Parms p = parms_from_problem(pr, scv);
+  const int N = p.max_batch;
+
+  double acc = 0.0;
+  for (int n = 0; n < N; ++n) {
+    acc += log_mu(p, n);
+    cum[n] = acc;
+  }
+  const double log_mu_n = log_mu(p, N - 1);
+  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
+  const double lam_max = serv_rate(p, N) * (1.0 - kEpsilon);
+
+  auto eval = [&](double lam) { return eval_model_compact(p, cum, log_mu_n, lam); };
+  auto eval_ttft = [&](double lam) { return eval_ttft_of(p, eval(lam)); };
+  auto eval_itl = [&](double lam) { return eval_itl_of(p, eval(lam)); };
+
+  double lam_ttft = lam_max;
+  if (pr[P_TARGET_TTFT] > 0.0) {
+    if (binary_search_host(lam_min, lam_max, pr[P_TARGET_TTFT], eval_ttft, &lam_ttft) < 0)
+      return;  // target below the bounded region: infeasible
+  }
+  double lam_itl = lam_max;
+  if (pr[P_TARGET_ITL] > 0.0) {
+    if (binary_search_host(lam_min, lam_max, pr[P_TARGET_ITL], eval_itl, &lam_itl) < 0)
+      return;
+  }
+  double lam_tps = lam_max;
+  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
+
+  double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
+  Stats st = eval(lam);
+  const double rate_star = st.throughput * 1000.0;  // req/s
+
+  const double total_rate = pr[P_TOTAL_RATE];
+  double n_rep = ceil(total_rate / rate_star);
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
+  if (!(n_rep > 0.0)) return;  // as in solve_one
+  const double rate = total_rate / n_rep;  // req/s per replica
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
+
+  Stats fin = eval(rate / 1000.0);
+  double rho = fin.n_serv / (double)N;
+  if (rho < 0.0) rho = 0.0;
+  if (rho > 1.0) rho = 1.0;
+
+  out[R_FEASIBLE] = 1.0;
+  out[R_REPLICAS] = n_rep;
+  out[R_RATE_STAR] = rate_star;
+  out[R_ITL] = eval_itl_of(p, fin);
+  out[R_TTFT] = eval_ttft_of(p, fin);
+  out[R_RHO] = rho;
+}
+
+// Table length solve_one_compact needs for a row: trunc(N), 0 if invalid.
+inline int row_compact_length(const double *pr) {
+  return row_valid(pr) ? (int)pr[P_MAX_BATCH] : 0;
+}
+
 }  // namespace wva

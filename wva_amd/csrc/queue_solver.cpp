@@ -120,12 +120,54 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
   return out;
 }
 
+// The host solve over the compact table (queue_host.h solve_one_compact): N
+// doubles of scratch per row instead of 11 * N.  CPU tensors only; on the GPU
+// the compact kernel is reached through submit_compact.
+static torch::Tensor solve_allocations_compact(
+    torch::Tensor problems, c10::optional<torch::Tensor> scv = c10::nullopt) {
+  TORCH_CHECK(problems.dim() == 2 && problems.size(1) == wva::PROBLEM_FIELDS,
+              "problems must be [B, ", (int)wva::PROBLEM_FIELDS, "]");
+  TORCH_CHECK(problems.scalar_type() == torch::kFloat64, "problems must be float64");
+  TORCH_CHECK(!problems.is_cuda(), "solve_allocations_compact takes CPU tensors");
+  problems = problems.contiguous();
+  const int64_t B = problems.size(0);
+  const double *scv_ptr = nullptr;
+  if (scv.has_value()) {
+    const torch::Tensor &v = *scv;
+    TORCH_CHECK(v.scalar_type() == torch::kFloat64, "scv must be float64");
+    TORCH_CHECK(v.dim() == 1 && v.size(0) == B, "scv must be [B] = [", B, "]");
+    TORCH_CHECK(v.is_contiguous(), "scv must be contiguous");
+    TORCH_CHECK(v.device() == problems.device(), "scv must be on the device of problems");
+    if (B > 0) scv_ptr = v.data_ptr<double>();
+  }
+  auto out = torch::zeros({B, (int64_t)wva::RESULT_FIELDS}, problems.options());
+  if (B == 0) return out;
+  const double *pr = problems.data_ptr<double>();
+  double *res = out.data_ptr<double>();
+  int max_n = 1;
+  for (int64_t i = 0; i < B; ++i) {
+    int n = wva::row_compact_length(pr + i * wva::PROBLEM_FIELDS);  // 0 if invalid
+    if (n > max_n) max_n = n;
+  }
+  at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
+    std::vector<double> cum((size_t)max_n);
+    for (int64_t i = begin; i < end; ++i) {
+      wva::solve_one_compact(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
+                             cum.data(), scv_ptr ? scv_ptr[i] : 1.0);
+    }
+  });
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "wva_amd native batched queue solver (CPU + gfx950 HIP)";
   m.def("solve_allocations", &solve_allocations,
         "Batched state-dependent M/M/1/K allocation sizing",
         pybind11::arg("problems"), pybind11::arg("max_k_hint") = -1,
         pybind11::arg("scv") = pybind11::none());
+  m.def("solve_allocations_compact", &solve_allocations_compact,
+        "The same sizing on the CPU over the compact table (N doubles per row)",
+        pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
 #ifdef WVA_WITH_HIP
@@ -135,6 +177,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "service-time cs^2) on the private dispatch stream; returns a ticket "
         "without waiting",
         pybind11::arg("problems"), pybind11::arg("max_k"),
+        pybind11::arg("scv") = pybind11::none());
+  m.def("submit_compact", &wva::dispatch::submit_compact,
+        "submit through the compact-table kernel: max_n is the largest max "
+        "batch N the launch reserves LDS for (N doubles, up to ~7800); same "
+        "slot pool, stream, checks and collect as submit",
+        pybind11::arg("problems"), pybind11::arg("max_n"),
         pybind11::arg("scv") = pybind11::none());
   m.def("collect", &wva::dispatch::collect,
         "Wait (GIL released) for a ticket and return its float64 [B, 6] results",

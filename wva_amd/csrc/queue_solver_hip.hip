@@ -32,7 +32,9 @@
 //   - LDS budget: (max_k + THREADS + 64) doubles <= 64 KiB for N <= ~700;
 //     the launcher checks it for the geometry it picked before launching
 //     and the binding raises when it does not fit (batched.py routes
-//     larger batch limits to the CPU path).
+//     larger batch limits to the CPU path, or — opt-in — to the
+//     compact-table kernel at the end of this file, which keeps N doubles
+//     instead of 11*N and reaches N ~7800).
 //
 // Numerics are double throughout, matching the Python analyzer; parity
 // is enforced by tests/test_ops.py, the @gpu numerics tests and
@@ -838,6 +840,207 @@ extern "C" __global__ void __launch_bounds__(128) wva_solve_kernel_128(
   solve_body_dual(prob, scv, out, n_problems, max_k);
 }
 
+// ---------------------------------------------------------------------------
+// Compact-table kernel: rows with max batch beyond the full table's LDS
+// limit (N up to ~7800 instead of ~700).
+//
+// LDS holds cum[0..N-1] only (queue_core.h, "Compact table"): the sweep
+// over the N+1 pre-batch states reads cum[n-1] with n-1 <= N-1, the mode is
+// at most N-1 or K, and log_p(N+1), log_p(K) and the geometric tail's
+// increment are closed form in L_N = log(serv_rate(N)).  One geometry: 256
+// threads, modelled on solve_body<256> — build_cum over N states, scalar
+// mode search, 4-wave strided 2x-unrolled sweeps (consecutive lanes on
+// consecutive doubles) with the LDS cross-wave combine, sequential TTFT then
+// ITL bisection.  Workgroup barriers only; control flow is uniform because
+// every evaluation result is the same on all threads.
+// LDS: (max_n + 256 + 64) doubles.
+// ---------------------------------------------------------------------------
+constexpr int kCompactThreads = 256;
+
+struct WgEvalCompact {
+  static constexpr int THREADS = kCompactThreads;
+  static constexpr int WAVES = THREADS / 64;
+  const Parms &p;
+  const double *cum;  // LDS, N entries
+  double *red;        // LDS scratch, WAVES * 5
+  double log_mu_n;    // L_N
+
+  __device__ Stats eval(double lam) const {
+    const int tid = threadIdx.x;
+    const int wave = tid >> 6;
+    const int lane = tid & 63;
+    const int num = p.max_batch;
+    const int K = num * (1 + kMaxQueueToBatchRatio);
+    const double loglam = log(lam);
+
+    const int n_star = log_mode_state(p, K, lam);
+    double m = log_p_compact(cum, num, log_mu_n, loglam, n_star);
+    if (m < 0.0) m = 0.0;
+    __syncthreads();  // red may still be read from a previous eval
+
+    // queue region (N, K] in closed form; uniform across lanes
+    const int g_start = num + 1;
+    const double d = loglam - log_mu_n;
+    const GeoTail tail = geo_tail_at(
+        log_p_compact(cum, num, log_mu_n, loglam, g_start) - m, d, g_start, K, K);
+    const int loop_hi = tail.used ? num : K;
+
+    // 2x-unrolled strided sweep, two independent exp chains per lane
+    double S = 0.0, Ni = 0.0, Snum = 0.0, Ninum = 0.0, eK = 0.0;
+    {
+      double S1 = 0.0, Ni1 = 0.0, Snum1 = 0.0, Ninum1 = 0.0, eK1 = 0.0;
+      int n = tid;
+      for (; n + THREADS <= loop_hi; n += 2 * THREADS) {
+        const int n2 = n + THREADS;
+        const double e = exp(log_p_compact(cum, num, log_mu_n, loglam, n) - m);
+        const double e2 = exp(log_p_compact(cum, num, log_mu_n, loglam, n2) - m);
+        S += e;
+        Ni += (double)n * e;
+        S1 += e2;
+        Ni1 += (double)n2 * e2;
+        if (n <= num) {
+          Snum += e;
+          Ninum += (double)n * e;
+        }
+        if (n2 <= num) {
+          Snum1 += e2;
+          Ninum1 += (double)n2 * e2;
+        }
+        if (n == K) eK = e;
+        if (n2 == K) eK1 = e2;
+      }
+      if (n <= loop_hi) {
+        const double e = exp(log_p_compact(cum, num, log_mu_n, loglam, n) - m);
+        S += e;
+        Ni += (double)n * e;
+        if (n <= num) {
+          Snum += e;
+          Ninum += (double)n * e;
+        }
+        if (n == K) eK = e;
+      }
+      S += S1;
+      Ni += Ni1;
+      Snum += Snum1;
+      Ninum += Ninum1;
+      eK += eK1;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      S += __shfl_down(S, off, 64);
+      Ni += __shfl_down(Ni, off, 64);
+      Snum += __shfl_down(Snum, off, 64);
+      Ninum += __shfl_down(Ninum, off, 64);
+      eK += __shfl_down(eK, off, 64);
+    }
+    if (lane == 0) {
+      red[wave * 5 + 0] = S;
+      red[wave * 5 + 1] = Ni;
+      red[wave * 5 + 2] = Snum;
+      red[wave * 5 + 3] = Ninum;
+      red[wave * 5 + 4] = eK;
+    }
+    __syncthreads();
+    S = Ni = Snum = Ninum = eK = 0.0;
+    for (int w = 0; w < WAVES; ++w) {
+      S += red[w * 5 + 0];
+      Ni += red[w * 5 + 1];
+      Snum += red[w * 5 + 2];
+      Ninum += red[w * 5 + 3];
+      eK += red[w * 5 + 4];
+    }
+    S += tail.S;
+    Ni += tail.Ni;
+    eK += tail.eK;
+    return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+  }
+
+  __device__ double eval_ttft(double lam) const { return eval_ttft_of(p, eval(lam)); }
+  __device__ double eval_itl(double lam) const { return eval_itl_of(p, eval(lam)); }
+};
+
+__device__ void solve_body_compact(const double *__restrict__ prob,
+                                   const double *__restrict__ scv,
+                                   double *__restrict__ out, int n_problems, int max_n) {
+  constexpr int THREADS = kCompactThreads;
+  const int pid = blockIdx.x;
+  if (pid >= n_problems) return;
+  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
+  double *res = out + (size_t)pid * RESULT_FIELDS;
+  const int tid = threadIdx.x;
+
+  // Row guard, before LDS is touched: the contract of queue_core.h and a
+  // table of trunc(N) <= max_n doubles.  The compare is on the double, so
+  // an N no int holds is rejected by row_valid before any cast.  The whole
+  // row is zeroed here; a valid row's six fields are overwritten at the end.
+  const double cs2 = row_scv(scv, pid);
+  const bool ok = row_valid(pr, cs2) & (trunc(pr[P_MAX_BATCH]) <= (double)max_n);
+  if (tid < RESULT_FIELDS) res[tid] = 0.0;
+  if (!ok) return;  // uniform: every thread reads the same row
+  const Parms p = parms_from_problem(pr, cs2);
+  const int N = p.max_batch;
+
+  extern __shared__ double smem[];
+  double *cum = smem;             // this problem's N entries
+  double *totals = smem + max_n;  // THREADS chunk totals
+  double *red = totals + THREADS;
+
+  build_cum<THREADS>(p, N, cum, totals);
+
+  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
+  const double lam_max = serv_rate(p, N) * (1.0 - kEpsilon);
+
+  WgEvalCompact ev{p, cum, red, log_mu(p, N - 1)};
+
+  double lam_ttft = lam_max;
+  if (pr[P_TARGET_TTFT] > 0.0) {
+    int ind = wg_binary_search(
+        lam_min, lam_max, pr[P_TARGET_TTFT],
+        [&](double x) { return ev.eval_ttft(x); }, &lam_ttft);
+    if (ind < 0) return;
+  }
+  double lam_itl = lam_max;
+  if (pr[P_TARGET_ITL] > 0.0) {
+    int ind = wg_binary_search(
+        lam_min, lam_max, pr[P_TARGET_ITL],
+        [&](double x) { return ev.eval_itl(x); }, &lam_itl);
+    if (ind < 0) return;
+  }
+  double lam_tps = lam_max;
+  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
+
+  const double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
+  Stats st = ev.eval(lam);
+  const double rate_star = st.throughput * 1000.0;  // req/s
+
+  const double total_rate = pr[P_TOTAL_RATE];
+  double n_rep = ceil(total_rate / rate_star);
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
+  if (!(n_rep > 0.0)) return;  // as in queue_host.h
+  const double rate = total_rate / n_rep;
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
+
+  Stats fin = ev.eval(rate / 1000.0);
+  double rho = fin.n_serv / (double)N;
+  rho = fmin(fmax(rho, 0.0), 1.0);
+
+  // the same thread range that zeroed the row writes it, so the two stores
+  // to a field come from one thread, in program order
+  if (tid < RESULT_FIELDS) {
+    const double vals[RESULT_FIELDS] = {1.0, n_rep, rate_star, eval_itl_of(p, fin),
+                                        eval_ttft_of(p, fin), rho};
+    double v = vals[0];
+    for (int f = 1; f < RESULT_FIELDS; ++f) v = (tid == f) ? vals[f] : v;
+    res[tid] = v;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(kCompactThreads) wva_solve_kernel_compact(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    double *__restrict__ out, int n_problems, int max_n) {
+  solve_body_compact(prob, scv, out, n_problems, max_n);
+}
+
 }  // namespace wva
 
 #include <cstdlib>
@@ -914,4 +1117,20 @@ extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, doubl
 extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
                                 int max_k, void *stream) {
   return wva_launch_solve_scv(prob, nullptr, out, n_problems, max_k, stream);
+}
+
+// Compact-table launch: max_n is the largest trunc(N) the launch reserves
+// LDS for (a row beyond it gets the all-zero row).  Same return values as
+// wva_launch_solve_scv: -1, before anything is launched, when cum[max_n] +
+// totals[256] + 64 slack doubles exceed 64 KiB.  One geometry;
+// WVA_GPU_THREADS does not apply.
+extern "C" int wva_launch_solve_compact(const double *prob, const double *scv, double *out,
+                                        int n_problems, int max_n, void *stream) {
+  const int lds_doubles = 64 * 1024 / 8;
+  if (max_n < 1 || max_n > lds_doubles - wva::kCompactThreads - 64) return -1;
+  const size_t smem = (size_t)(max_n + wva::kCompactThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_solve_kernel_compact, dim3(n_problems),
+                     dim3(wva::kCompactThreads), smem, (hipStream_t)stream, prob, scv, out,
+                     n_problems, max_n);
+  return (int)hipGetLastError();
 }

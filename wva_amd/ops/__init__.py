@@ -82,7 +82,12 @@ def get_native():
     return None
 
 
-from .batched import BatchedAllocationSolver, solve_problems  # noqa: E402
+from .batched import (  # noqa: E402
+    GPU_COMPACT_MAX_BATCH_LIMIT,
+    GPU_MAX_BATCH_LIMIT,
+    BatchedAllocationSolver,
+    solve_problems,
+)
 
 __all__ = [
     "native_available",
@@ -91,4 +96,6 @@ __all__ = [
     "get_native_cpu",
     "BatchedAllocationSolver",
     "solve_problems",
+    "GPU_MAX_BATCH_LIMIT",
+    "GPU_COMPACT_MAX_BATCH_LIMIT",
 ]

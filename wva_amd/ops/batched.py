@@ -15,6 +15,9 @@ environment's fleet value.  On the GPU the matrix travels through the native
 submit/collect dispatch (csrc/sizing_dispatch.h), and
 ``BatchedAllocationSolver`` may cut the fleet into chunks so that its own
 per-row host work overlaps the launches (docs/design/native-queue-solver.md).
+Rows whose max batch exceeds GPU_MAX_BATCH_LIMIT leave the GPU for the CPU
+solver unless the ``large_n`` opt-in (``WVA_GPU_LARGE_N=1``) sends them to the
+compact-table kernel (same document, "Compact table").
 
 Field layouts mirror wva_amd/csrc/queue_core.h, and so does the row
 contract (``row_valid`` there, ``valid_rows`` here).  A row is valid iff
@@ -86,6 +89,10 @@ RESULT_FIELDS = 6
 # the GPU path keeps the cumulative table in LDS: N <= ~700
 GPU_MAX_BATCH_LIMIT = 700
 
+# the compact-table kernel keeps only cum[0..N-1] there (csrc/queue_core.h):
+# N + 256 + 64 doubles in 64 KiB allow 7872, rounded down to a multiple of 256
+GPU_COMPACT_MAX_BATCH_LIMIT = 7680
+
 # largest N whose chain length 11 * N fits a C int (queue_core.h kMaxBatchLimit)
 _MAX_BATCH_LIMIT = (2**31 - 1) // (1 + MAX_QUEUE_TO_BATCH_RATIO)
 
@@ -143,6 +150,16 @@ _mg1_warned = False
 
 def _graph_requested() -> bool:
     return not _graph_disabled and os.environ.get("WVA_GPU_GRAPH", "0") == "1"
+
+
+def _large_n_requested(large_n: Optional[bool]) -> bool:
+    """Whether rows with GPU_MAX_BATCH_LIMIT < N <= GPU_COMPACT_MAX_BATCH_LIMIT
+    go to the compact-table kernel instead of the CPU split: the caller's
+    ``large_n``, or for ``None`` the environment (``WVA_GPU_LARGE_N=1``, read
+    per call).  Off by default.  The hipGraph route keeps the CPU split."""
+    if large_n is None:
+        large_n = os.environ.get("WVA_GPU_LARGE_N", "0") == "1"
+    return bool(large_n) and not _graph_requested()
 
 
 _NO_DEVICE_SWITCH = contextlib.nullcontext()
@@ -211,6 +228,87 @@ def _graph_solve(native, problems_t, max_k, scv_t=None):
             return None
 
 
+class _LargeNTicket:
+    """One chunk split by max batch N (the ``large_n`` opt-in), in flight.
+
+    - rows with N <= GPU_MAX_BATCH_LIMIT, and invalid rows, went to
+      ``native.submit`` with the max_k of those rows alone, so they get the
+      geometry and the results they get without the opt-in, bit for bit;
+    - valid rows up to GPU_COMPACT_MAX_BATCH_LIMIT went to
+      ``native.submit_compact`` as a second launch;
+    - valid rows beyond that were solved on the CPU while both launches ran.
+
+    Each part carried the cs^2 of its own rows.  ``collect`` waits for both
+    launches and merges the three parts back in row order."""
+
+    def __init__(self, native, device, problems, batch_limits, scv_arr):
+        n_rows = problems.shape[0]
+        small = batch_limits <= GPU_MAX_BATCH_LIMIT
+        big = batch_limits > GPU_COMPACT_MAX_BATCH_LIMIT
+        middle = ~(small | big)
+        self.n_rows = n_rows
+        self.parts = []  # (row mask, native ticket)
+        self.big = big
+        self.big_solved = None
+
+        def part(mask):
+            rows = np.ascontiguousarray(problems[mask])
+            return rows, (None if scv_arr is None else np.ascontiguousarray(scv_arr[mask]))
+
+        try:
+            with _on_device(device):
+                if small.any():
+                    rows, scv = part(small)
+                    # solve_problems' max_k rule on these rows alone: the raw
+                    # column unless an invalid row's N is a NaN or too large
+                    max_batch = rows[:, P_MAX_BATCH].max()
+                    if not max_batch <= GPU_MAX_BATCH_LIMIT:
+                        max_batch = batch_limits[small].max()
+                    max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
+                    args = (rows, max_k) if scv is None else (rows, max_k, scv)
+                    self.parts.append((small, native.submit(*args)))
+                if middle.any():
+                    rows, scv = part(middle)
+                    max_n = int(batch_limits[middle].max())
+                    args = (rows, max_n) if scv is None else (rows, max_n, scv)
+                    self.parts.append((middle, native.submit_compact(*args)))
+            if big.any():
+                rows, scv = part(big)
+                if scv is None:
+                    self.big_solved = solve_problems(rows, device="cpu")
+                else:
+                    self.big_solved = solve_problems(rows, device="cpu", scv=scv)
+        except BaseException:
+            # a launch already enqueued must not keep its slot for good
+            for _, ticket in self.parts:
+                try:
+                    native.collect(ticket)
+                except Exception:
+                    pass
+            raise
+
+    def collect(self, native) -> np.ndarray:
+        out = np.empty((self.n_rows, RESULT_FIELDS), dtype=np.float64)
+        parts, self.parts = self.parts, []
+        error = None
+        for mask, ticket in parts:  # every ticket is collected, whatever happens
+            try:
+                out[mask] = native.collect(ticket)
+            except Exception as e:  # pragma: no cover - needs a failing GPU
+                error = error or e
+        if error is not None:
+            raise error
+        if self.big_solved is not None:
+            out[self.big] = self.big_solved
+        return out
+
+
+def _valid_batch_limits(problems: np.ndarray) -> np.ndarray:
+    """Column N with the invalid rows' entries replaced by 1, so that they
+    neither size a launch nor leave the GPU."""
+    return np.where(valid_rows(problems), problems[:, P_MAX_BATCH], 1.0)
+
+
 def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
     """Reference-semantics scalar fallback via the Python analyzer.
 
@@ -266,7 +364,8 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
 
 
 def solve_problems(
-    problems: np.ndarray, device: Optional[str] = None, scv=None
+    problems: np.ndarray, device: Optional[str] = None, scv=None,
+    large_n: Optional[bool] = None,
 ) -> np.ndarray:
     """Solve a [B, 12] problem matrix -> [B, 6] results.
 
@@ -281,6 +380,13 @@ def solve_problems(
     binding; the Python analyzer only when nothing native is built).
     ``None`` is the Markovian model, except under ``WVA_ANALYZER=mg1``,
     where the environment's fleet value goes through the Python analyzer.
+
+    large_n: on the GPU, whether valid rows with GPU_MAX_BATCH_LIMIT < N <=
+    GPU_COMPACT_MAX_BATCH_LIMIT run on the compact-table kernel (a second
+    launch, enqueued together with the first) instead of the CPU.  ``None``
+    asks the environment (``WVA_GPU_LARGE_N=1``), ``False`` forces the CPU
+    split.  Off by default; no effect on the CPU, on rows within
+    GPU_MAX_BATCH_LIMIT, or under ``WVA_GPU_GRAPH=1``.
     """
     from . import get_native, native_available
 
@@ -326,6 +432,11 @@ def solve_problems(
         if not max_batch <= GPU_MAX_BATCH_LIMIT:
             batch_limits = np.where(valid_rows(problems), batch_limits, 1.0)
             max_batch = batch_limits.max()
+        if max_batch > GPU_MAX_BATCH_LIMIT and _large_n_requested(large_n):
+            # opt-in: a second, compact-table launch takes the rows up to
+            # GPU_COMPACT_MAX_BATCH_LIMIT; only rows beyond it leave the GPU
+            split = _LargeNTicket(native, device, problems, batch_limits, scv_arr)
+            return split.collect(native)
         if max_batch > GPU_MAX_BATCH_LIMIT:
             # LDS-resident limit: solve oversized problems on CPU
             big = batch_limits > GPU_MAX_BATCH_LIMIT
@@ -445,6 +556,33 @@ class NativeGpuDispatch:
         return self.native.collect(native_ticket)
 
 
+class LargeNGpuDispatch(NativeGpuDispatch):
+    """NativeGpuDispatch under the ``large_n`` opt-in (``solve_problems``):
+    a chunk with a valid row above GPU_MAX_BATCH_LIMIT stays asynchronous, its
+    rows up to GPU_COMPACT_MAX_BATCH_LIMIT going to the compact-table kernel
+    as a second launch (``_LargeNTicket``).  Any other chunk takes the parent
+    class's path unchanged.  ``BatchedAllocationSolver`` picks this class only
+    when the opt-in is on, so the default pipeline runs the class above as it
+    always did."""
+
+    def submit(self, problems: np.ndarray, scv_rows=None):
+        if not problems[:, P_MAX_BATCH].max() <= GPU_MAX_BATCH_LIMIT:  # also a NaN N
+            batch_limits = _valid_batch_limits(problems)
+            if batch_limits.max() > GPU_MAX_BATCH_LIMIT:
+                scv_arr = None
+                if self.global_scv is not None:
+                    scv_arr = _resolved_scv(scv_rows, self.global_scv)
+                return _LargeNTicket(self.native, self.device, problems, batch_limits,
+                                     scv_arr), None
+            # only an invalid row has the large N: the parent class's path
+        return super().submit(problems, scv_rows)
+
+    def collect(self, ticket) -> np.ndarray:
+        if isinstance(ticket[0], _LargeNTicket):
+            return ticket[0].collect(self.native)
+        return super().collect(ticket)
+
+
 # Chunks the GPU pipeline splits a fleet into when the caller does not say
 # (measured on the flagship shape: profiles/async_dispatch.md).
 DEFAULT_GPU_CHUNKS = 2
@@ -472,14 +610,19 @@ class BatchedAllocationSolver:
     call.  A fleet in which some server may need the M/G/1 correction
     (``WVA_ANALYZER=mg1`` or a measured ``service_scv``) carries one cs^2 per
     row through the same dispatch; on the GPU it is chunked like any other
-    fleet, elsewhere it is one chunk.
+    fleet, elsewhere it is one chunk.  ``large_n`` is ``solve_problems``'
+    opt-in for servers whose max batch exceeds GPU_MAX_BATCH_LIMIT: their
+    rows run on the compact-table kernel and their chunk stays asynchronous
+    (``None`` asks ``WVA_GPU_LARGE_N``; no effect off the GPU).
     """
 
-    def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None) -> None:
+    def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None,
+                 large_n: Optional[bool] = None) -> None:
         if chunks is not None and chunks < 1:
             raise ValueError("chunks must be at least 1")
         self.device = device
         self.chunks = chunks
+        self.large_n = large_n
 
     def _plan(self, system: System, servers):
         """The dispatch and chunk count for this fleet, decided before any
@@ -502,6 +645,8 @@ class BatchedAllocationSolver:
             chunks = self.chunks if self.chunks is not None else DEFAULT_GPU_CHUNKS
             if len(servers) * len(system.accelerators) >= _GPU_CHUNKING_ROW_BOUND:
                 chunks = 1
+            if _large_n_requested(self.large_n):
+                return LargeNGpuDispatch(native, self.device, dispatch_scv), chunks, track_scv
             return NativeGpuDispatch(native, self.device, dispatch_scv), chunks, track_scv
         if track_scv:
             return SyncDispatch(self.device, dispatch_scv), 1, True
