@@ -277,12 +277,12 @@ struct GeoTail {
   bool used;
 };
 
-WVA_HD GeoTail geo_tail(const double *cum, double loglam, double d, double m,
-                        int g_start, int n_hi, int K) {
+// x_a = log_p(g_start) - m is the first term's exponent; the caller takes it
+// from its table (a full table reads an entry, a compact one has none).
+WVA_HD GeoTail geo_tail(double x_a, double d, int g_start, int n_hi, int K) {
   GeoTail t{0.0, 0.0, 0.0, false};
   const int M = n_hi - g_start;
   if (M < 8 || fabs(d) * (double)(M + 1) < 0.01) return t;  // loop is fine/safer
-  const double x_a = log_p(cum, loglam, g_start) - m;
   const double p_a = exp(x_a);
   const double e1 = expm1(d);
   const double G0 = expm1((double)(M + 1) * d) / e1;
@@ -295,6 +295,25 @@ WVA_HD GeoTail geo_tail(const double *cum, double loglam, double d, double m,
   if (n_hi == K) t.eK = p_a * exp((double)(K - g_start) * d);
   t.used = true;
   return t;
+}
+
+// Stats from the reduced state sums: the closing arithmetic of every model
+// evaluation, host and device
+WVA_HD Stats stats_of_sums(double lam, int num, double S, double Ni, double Snum,
+                           double Ninum, double eK) {
+  Stats st;
+  st.throughput = lam * (1.0 - eK / S);
+  double n_sys = Ni / S;
+  st.n_serv = Ninum / S + (1.0 - Snum / S) * (double)num;
+  if (st.throughput == 0.0) {
+    st.wait = st.serv = 0.0;
+  } else {
+    double resp = n_sys / st.throughput;
+    st.serv = st.n_serv / st.throughput;
+    st.wait = resp - st.serv;
+    if (st.wait < 0.0) st.wait = 0.0;
+  }
+  return st;
 }
 
 // Scalar model evaluation at arrival rate lam (req/ms) given the inclusive
@@ -315,7 +334,7 @@ WVA_HD Stats eval_model(const Parms &p, const double *cum, int K, double lam) {
   int loop_hi = n_hi;
   if (g_start + 8 <= n_hi) {  // also keeps cum[g_start] in bounds
     const double d = loglam - (cum[g_start] - cum[g_start - 1]);
-    tail = geo_tail(cum, loglam, d, m, g_start, n_hi, K);
+    tail = geo_tail(log_p(cum, loglam, g_start) - m, d, g_start, n_hi, K);
     if (tail.used) loop_hi = g_start - 1;
   }
   for (int n = n_lo; n <= loop_hi; ++n) {
@@ -331,19 +350,7 @@ WVA_HD Stats eval_model(const Parms &p, const double *cum, int K, double lam) {
   S += tail.S;
   Ni += tail.Ni;
   eK += tail.eK;
-  Stats st;
-  st.throughput = lam * (1.0 - eK / S);
-  double n_sys = Ni / S;
-  st.n_serv = Ninum / S + (1.0 - Snum / S) * num;
-  if (st.throughput == 0.0) {
-    st.wait = st.serv = 0.0;
-  } else {
-    double resp = n_sys / st.throughput;
-    st.serv = st.n_serv / st.throughput;
-    st.wait = resp - st.serv;
-    if (st.wait < 0.0) st.wait = 0.0;
-  }
-  return st;
+  return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
 }
 
 // ---------------------------------------------------------------------------
@@ -375,48 +382,24 @@ WVA_HD double log_p_compact(const double *cum, int N, double log_mu_n, double lo
   return (n == 0) ? 0.0 : n * loglam - cum_at(cum, N, log_mu_n, n - 1);
 }
 
-// geo_tail with the first term's exponent x_a = log_p(g_start) - m given by
-// the caller (the compact table has no entry to read it from)
-WVA_HD GeoTail geo_tail_at(double x_a, double d, int g_start, int n_hi, int K) {
-  GeoTail t{0.0, 0.0, 0.0, false};
-  const int M = n_hi - g_start;
-  if (M < 8 || fabs(d) * (double)(M + 1) < 0.01) return t;  // loop is fine/safer
-  const double p_a = exp(x_a);
-  const double e1 = expm1(d);
-  const double G0 = expm1((double)(M + 1) * d) / e1;
-  const double r = e1 + 1.0;
-  const double rM = exp((double)M * d);
-  const double G1 =
-      r * (1.0 - (double)(M + 1) * rM + (double)M * rM * r) / (e1 * e1);
-  t.S = p_a * G0;
-  t.Ni = p_a * ((double)g_start * G0 + G1);
-  if (n_hi == K) t.eK = p_a * exp((double)(K - g_start) * d);
-  t.used = true;
-  return t;
-}
-
-// Stats from the reduced state sums (the closing arithmetic of eval_model)
-WVA_HD Stats stats_of_sums(double lam, int num, double S, double Ni, double Snum,
-                           double Ninum, double eK) {
-  Stats st;
-  st.throughput = lam * (1.0 - eK / S);
-  double n_sys = Ni / S;
-  st.n_serv = Ninum / S + (1.0 - Snum / S) * (double)num;
-  if (st.throughput == 0.0) {
-    st.wait = st.serv = 0.0;
-  } else {
-    double resp = n_sys / st.throughput;
-    st.serv = st.n_serv / st.throughput;
-    st.wait = resp - st.serv;
-    if (st.wait < 0.0) st.wait = 0.0;
-  }
-  return st;
+// The compact table's tail over the whole queue region (N, K], host and
+// device: d is taken directly, and *loop_hi is where the term-wise sweep
+// stops (N, or K where the tail declines).
+WVA_HD GeoTail geo_tail_compact(const double *cum, int N, double log_mu_n, double loglam,
+                                double m, int *loop_hi) {
+  const int K = N * (1 + kMaxQueueToBatchRatio);
+  const int g_start = N + 1;
+  const double d = loglam - log_mu_n;
+  const GeoTail tail = geo_tail(
+      log_p_compact(cum, N, log_mu_n, loglam, g_start) - m, d, g_start, K, K);
+  *loop_hi = tail.used ? N : K;
+  return tail;
 }
 
 // eval_model over the compact table cum[0..N-1] (same inclusive sum), with
 // log_mu_n = log_mu(p, N-1).  No significance window: the sweep covers the
 // N+1 pre-batch states and the queue region (N, K] sums in closed form; only
-// where geo_tail_at declines (|d| * 10N < 0.01, a sliver around lam = mu(N))
+// where geo_tail declines (|d| * 10N < 0.01, a sliver around lam = mu(N))
 // does the loop run on to K through cum_at.
 WVA_HD Stats eval_model_compact(const Parms &p, const double *cum, double log_mu_n,
                                 double lam) {
@@ -426,11 +409,8 @@ WVA_HD Stats eval_model_compact(const Parms &p, const double *cum, double log_mu
   const int n_star = log_mode_state(p, K, lam);  // in [0, N-1], or K
   double m = log_p_compact(cum, num, log_mu_n, loglam, n_star);
   if (m < 0.0) m = 0.0;  // logp(0) = 0 participates in the max
-  const int g_start = num + 1;
-  const double d = loglam - log_mu_n;
-  const GeoTail tail = geo_tail_at(
-      log_p_compact(cum, num, log_mu_n, loglam, g_start) - m, d, g_start, K, K);
-  const int loop_hi = tail.used ? num : K;
+  int loop_hi;
+  const GeoTail tail = geo_tail_compact(cum, num, log_mu_n, loglam, m, &loop_hi);
   double S = 0.0, Ni = 0.0, Snum = 0.0, Ninum = 0.0, eK = 0.0;
   for (int n = 0; n <= loop_hi; ++n) {
     double e = exp(log_p_compact(cum, num, log_mu_n, loglam, n) - m);
@@ -456,6 +436,162 @@ WVA_HD double eval_ttft_of(const Parms &p, const Stats &st) {
 WVA_HD double eval_itl_of(const Parms &p, const Stats &st) {
   double effc = effective_concurrency(p, st.serv);
   return decode_time(p, effc);
+}
+
+// ---------------------------------------------------------------------------
+// Monotone bisection mirroring analyzer/search.py: boundary classification
+// -1 below / 0 within / +1 above, relative tolerance, 100 iterations.
+// ---------------------------------------------------------------------------
+
+constexpr int kBisect = 2;  // classify_bracket: the target lies strictly inside
+
+// Classifies a bracket from its two end values y0 = y(x_min), y1 = y(x_max).
+// Returns the indicator with *x_star set, or kBisect with *increasing set.
+WVA_HD int classify_bracket(double x_min, double x_max, double y0, double y1,
+                            double y_target, double *x_star, bool *increasing) {
+  if (within_tolerance(y0, y_target, kTolerance)) {
+    *x_star = x_min;
+    return 0;
+  }
+  if (within_tolerance(y1, y_target, kTolerance)) {
+    *x_star = x_max;
+    return 0;
+  }
+  if (within_tolerance(y0, y1, kTolerance)) {
+    // flat function: classify by value only (direction would be noise)
+    if (y_target > fmax(y0, y1)) {
+      *x_star = x_max;
+      return +1;
+    }
+    *x_star = x_min;
+    return -1;
+  }
+  *increasing = y0 < y1;
+  if ((*increasing && y_target < y0) || (!*increasing && y_target > y0)) {
+    *x_star = x_min;
+    return -1;
+  }
+  if ((*increasing && y_target > y1) || (!*increasing && y_target < y1)) {
+    *x_star = x_max;
+    return +1;
+  }
+  return kBisect;
+}
+
+// Both bracket ends are evaluated before anything is classified, as the
+// speculative search does.  Earlier sequential searches returned after
+// y(x_min) when it already met the target within the tolerance; such a row
+// now costs one evaluation more and gets the same answer, because the
+// classification tests y0 first.
+// On the device every thread that shares an evaluator runs this in lockstep:
+// the eval results are identical on all of them because they come from
+// broadcast reductions, so the control flow is uniform.
+template <typename F>
+WVA_HD int binary_search(double x_min, double x_max, double y_target, F eval,
+                         double *x_star) {
+  const double y0 = eval(x_min);
+  const double y1 = eval(x_max);
+  bool increasing = false;
+  const int ind = classify_bracket(x_min, x_max, y0, y1, y_target, x_star, &increasing);
+  if (ind != kBisect) return ind;
+  double xs = x_min;
+  for (int i = 0; i < kMaxIterations; ++i) {
+    xs = 0.5 * (x_min + x_max);
+    double ys = eval(xs);
+    if (within_tolerance(ys, y_target, kTolerance)) break;
+    // (spelled out, here and in the speculative walk: behind a helper the
+    // compiler no longer specialises the loop on `increasing`, and the
+    // 256-thread kernels lose a wave per SIMD to the extra registers)
+    if ((increasing && y_target < ys) || (!increasing && y_target > ys)) {
+      x_max = xs;
+    } else {
+      x_min = xs;
+    }
+  }
+  *x_star = xs;
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Row solve: the non-zero-load body of core.create_allocation over any
+// evaluator, i.e. anything with eval(lam) -> Stats (host table, LDS table,
+// one wave or a workgroup).  Two parts, so that a kernel that runs the two
+// searches its own way can use the second alone.
+// ---------------------------------------------------------------------------
+
+// rate range of the searches, req/ms
+WVA_HD void rate_bracket(const Parms &p, double *lam_min, double *lam_max) {
+  *lam_min = serv_rate(p, 1) * kEpsilon;
+  *lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
+}
+
+// Part 1: the TTFT search, then the ITL search.  False when a target lies
+// below the bounded region: the row is infeasible.
+template <typename Ev>
+WVA_HD bool search_targets(const double *pr, const Parms &p, const Ev &ev, double lam_min,
+                           double lam_max, double *lam_ttft, double *lam_itl) {
+  *lam_ttft = lam_max;
+  if (pr[P_TARGET_TTFT] > 0.0) {
+    auto ttft = [&](double lam) { return eval_ttft_of(p, ev.eval(lam)); };
+    if (binary_search(lam_min, lam_max, pr[P_TARGET_TTFT], ttft, lam_ttft) < 0) return false;
+  }
+  *lam_itl = lam_max;
+  if (pr[P_TARGET_ITL] > 0.0) {
+    auto itl = [&](double lam) { return eval_itl_of(p, ev.eval(lam)); };
+    if (binary_search(lam_min, lam_max, pr[P_TARGET_ITL], itl, lam_itl) < 0) return false;
+  }
+  return true;
+}
+
+// One result row by value, in ResultField order; RowValues{} is the all-zero
+// row of an infeasible or rejected problem.  Named fields, returned by value
+// and not through memory: the kernels pick one field per thread, and values
+// that live behind a pointer there end up in scratch memory, not registers.
+struct RowValues {
+  double feasible, replicas, rate_star, itl, ttft, rho;
+};
+
+// Part 2: from the two searched rates (and the TPS back-off) to the result
+// row.  Knows nothing about threads: every thread that shares ev runs it and
+// gets the same answer.
+template <typename Ev>
+WVA_HD RowValues row_tail(const double *pr, const Parms &p, const Ev &ev, double lam_max,
+                          double lam_ttft, double lam_itl) {
+  double lam_tps = lam_max;
+  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
+
+  const double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
+  Stats st = ev.eval(lam);
+  const double rate_star = st.throughput * 1000.0;  // req/s
+
+  const double total_rate = pr[P_TOTAL_RATE];
+  double n_rep = ceil(total_rate / rate_star);
+  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
+  if (n_rep < min_rep) n_rep = min_rep;
+  // no replicas, or a per-replica rate that is not > 0 (zero or negative
+  // load; NaN from 0/0 fails every ordered compare): infeasible
+  if (!(n_rep > 0.0)) return RowValues{};
+  const double rate = total_rate / n_rep;  // req/s per replica
+  if (!(rate > 0.0) || rate > lam_max * 1000.0) return RowValues{};
+
+  Stats fin = ev.eval(rate / 1000.0);
+  double rho = fin.n_serv / (double)p.max_batch;
+  // The kernels' form of the clamp, on the host as well (which used two
+  // ifs): a NaN rho comes out as 0 and -0.0 as +0.0, where the ifs passed
+  // both through.  A NaN cannot arise here: rate <= lam_max keeps the tail's
+  // d negative and every sum finite.
+  rho = fmin(fmax(rho, 0.0), 1.0);
+
+  return RowValues{1.0, n_rep, rate_star, eval_itl_of(p, fin), eval_ttft_of(p, fin), rho};
+}
+
+// Both parts over one evaluator.
+template <typename Ev>
+WVA_HD RowValues solve_row(const double *pr, const Parms &p, const Ev &ev) {
+  double lam_min, lam_max, lam_ttft, lam_itl;
+  rate_bracket(p, &lam_min, &lam_max);
+  if (!search_targets(pr, p, ev, lam_min, lam_max, &lam_ttft, &lam_itl)) return RowValues{};
+  return row_tail(pr, p, ev, lam_max, lam_ttft, lam_itl);
 }
 
 }  // namespace wva

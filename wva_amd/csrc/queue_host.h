@@ -3,7 +3,8 @@
 // and the torch-free pybind11/numpy binding (queue_solver_cpu.cpp) used
 // in the slim controller image.  Semantics mirror
 // core.create_allocation's non-zero-load body (see queue_solver.cpp's
-// header comment for the reference citation).
+// header comment for the reference citation); the solve itself is
+// queue_core.h's solve_row, here over a table in host memory.
 #pragma once
 
 #include <cmath>
@@ -13,180 +14,79 @@
 
 namespace wva {
 
-// Monotone bisection mirroring analyzer/search.py (boundary classification
-// -1 below / 0 within / +1 above, relative tolerance, 100 iterations).
-template <typename F>
-inline int binary_search_host(double x_min, double x_max, double y_target, F eval,
-                              double *x_star) {
-  double y0 = eval(x_min);
-  if (within_tolerance(y0, y_target, kTolerance)) {
-    *x_star = x_min;
-    return 0;
-  }
-  double y1 = eval(x_max);
-  if (within_tolerance(y1, y_target, kTolerance)) {
-    *x_star = x_max;
-    return 0;
-  }
-  if (within_tolerance(y0, y1, kTolerance)) {
-    // flat function: classify by value only (direction would be noise)
-    if (y_target > fmax(y0, y1)) {
-      *x_star = x_max;
-      return +1;
-    }
-    *x_star = x_min;
-    return -1;
-  }
-  bool increasing = y0 < y1;
-  if ((increasing && y_target < y0) || (!increasing && y_target > y0)) {
-    *x_star = x_min;
-    return -1;
-  }
-  if ((increasing && y_target > y1) || (!increasing && y_target < y1)) {
-    *x_star = x_max;
-    return +1;
-  }
-  double xs = x_min;
-  for (int i = 0; i < kMaxIterations; ++i) {
-    xs = 0.5 * (x_min + x_max);
-    double ys = eval(xs);
-    if (within_tolerance(ys, y_target, kTolerance)) break;
-    if ((increasing && y_target < ys) || (!increasing && y_target > ys)) {
-      x_max = xs;
-    } else {
-      x_min = xs;
-    }
-  }
-  *x_star = xs;
-  return 0;
+// Table length the compact policy needs for a row: trunc(N), 0 if invalid.
+inline int row_compact_length(const double *pr) {
+  return row_valid(pr) ? (int)pr[P_MAX_BATCH] : 0;
 }
 
-// Scalar solve of one problem (CPU path).  cum must hold
-// row_chain_length(pr) doubles; a row that breaks the contract of
-// queue_core.h yields the all-zero row and touches no table.  scv is the
-// row's service-time cs^2 (1.0: Markovian); it only enters through
-// Parms::wait_scale in eval_ttft_of.
+// inclusive sum cum[n] = sum_{i<=n} log_mu(i) over the first `len` states
+inline void fill_cum(const Parms &p, int len, double *cum) {
+  double acc = 0.0;
+  for (int n = 0; n < len; ++n) {
+    acc += log_mu(p, n);
+    cum[n] = acc;
+  }
+}
+
+// Table policies of solve_one: how long a row's table is, how it is filled,
+// and which eval_model* reads it.  Each is an evaluator for solve_row.  The
+// constructor WRITES the caller's scratch table (the log_mu scan) and the
+// object then only reads it.
+
+// K = 11 * N doubles, evaluated inside the significance window (state_window)
+struct HostFullTable {
+  static int length(const double *pr) { return row_chain_length(pr); }
+  const Parms &p;
+  const double *cum;
+  int K;
+  HostFullTable(const Parms &parms, double *table)
+      : p(parms), cum(table), K(parms.max_batch * (1 + kMaxQueueToBatchRatio)) {
+    fill_cum(p, K, table);
+  }
+  Stats eval(double lam) const { return eval_model(p, cum, K, lam); }
+};
+
+// N doubles (queue_core.h, "Compact table"); no window
+struct HostCompactTable {
+  static int length(const double *pr) { return row_compact_length(pr); }
+  const Parms &p;
+  const double *cum;
+  double log_mu_n;
+  HostCompactTable(const Parms &parms, double *table)
+      : p(parms), cum(table), log_mu_n(log_mu(parms, parms.max_batch - 1)) {
+    fill_cum(p, p.max_batch, table);
+  }
+  Stats eval(double lam) const { return eval_model_compact(p, cum, log_mu_n, lam); }
+};
+
+// Scalar solve of one problem (CPU path).  cum must hold Table::length(pr)
+// doubles; a row that breaks the contract of queue_core.h yields the
+// all-zero row and touches no table.  scv is the row's service-time cs^2
+// (1.0: Markovian); it only enters through Parms::wait_scale in eval_ttft_of.
+template <typename Table>
 inline void solve_one(const double *pr, double *out, double *cum, double scv = 1.0) {
   for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
   if (!row_valid(pr, scv)) return;
-  Parms p = parms_from_problem(pr, scv);
-  const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
-
-  double acc = 0.0;
-  for (int n = 0; n < K; ++n) {
-    acc += log_mu(p, n);
-    cum[n] = acc;
-  }
-  const double lam_min = serv_rate(p, 1) * kEpsilon;           // req/ms
-  const double lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
-
-  auto eval_ttft = [&](double lam) { return eval_ttft_of(p, eval_model(p, cum, K, lam)); };
-  auto eval_itl = [&](double lam) { return eval_itl_of(p, eval_model(p, cum, K, lam)); };
-
-  double lam_ttft = lam_max;
-  if (pr[P_TARGET_TTFT] > 0.0) {
-    if (binary_search_host(lam_min, lam_max, pr[P_TARGET_TTFT], eval_ttft, &lam_ttft) < 0)
-      return;  // target below the bounded region: infeasible
-  }
-  double lam_itl = lam_max;
-  if (pr[P_TARGET_ITL] > 0.0) {
-    if (binary_search_host(lam_min, lam_max, pr[P_TARGET_ITL], eval_itl, &lam_itl) < 0)
-      return;
-  }
-  double lam_tps = lam_max;
-  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
-
-  double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
-  Stats st = eval_model(p, cum, K, lam);
-  const double rate_star = st.throughput * 1000.0;  // req/s
-
-  const double total_rate = pr[P_TOTAL_RATE];
-  double n_rep = ceil(total_rate / rate_star);
-  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
-  if (n_rep < min_rep) n_rep = min_rep;
-  // no replicas, or a per-replica rate that is not > 0 (zero or negative
-  // load; NaN from 0/0 fails every ordered compare): infeasible
-  if (!(n_rep > 0.0)) return;
-  const double rate = total_rate / n_rep;  // req/s per replica
-  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
-
-  Stats fin = eval_model(p, cum, K, rate / 1000.0);
-  double rho = fin.n_serv / (double)p.max_batch;
-  if (rho < 0.0) rho = 0.0;
-  if (rho > 1.0) rho = 1.0;
-
-  out[R_FEASIBLE] = 1.0;
-  out[R_REPLICAS] = n_rep;
-  out[R_RATE_STAR] = rate_star;
-  out[R_ITL] = eval_itl_of(p, fin);
-  out[R_TTFT] = eval_ttft_of(p, fin);
-  out[R_RHO] = rho;
+  const Parms p = parms_from_problem(pr, scv);
+  const Table table(p, cum);  // fills cum: the O(table length) build happens here
+  const RowValues vals = solve_row(pr, p, table);
+  out[R_FEASIBLE] = vals.feasible;
+  out[R_REPLICAS] = vals.replicas;
+  out[R_RATE_STAR] = vals.rate_star;
+  out[R_ITL] = vals.itl;
+  out[R_TTFT] = vals.ttft;
+  out[R_RHO] = vals.rho;
 }
 
-// solve_one over the compact table (queue_core.h, eval_model_compact): cum
-// must hold trunc(N) doubles for a valid row, and nothing is touched for an
-// invalid one.  Same semantics, same row contract, same result layout.
-inline void solve_one_compact(const double *pr, double *out, double *cum,
-                              double scv = 1.0) {
-  for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
-  if (!row_valid(pr, scv)) return;
-  Parms p = parms_from_problem(pr, scv);
-  const int N = p.max_batch;
-
-  double acc = 0.0;
-  for (int n = 0; n < N; ++n) {
-    acc += log_mu(p, n);
-    cum[n] = acc;
+// Scratch one thread needs for any row of a batch: the longest table, >= 1.
+template <typename Table>
+inline int batch_table_length(const double *pr, long long rows) {
+  int longest = 1;
+  for (long long i = 0; i < rows; ++i) {
+    const int len = Table::length(pr + i * PROBLEM_FIELDS);  // 0 if invalid
+    if (len > longest) longest = len;
   }
-  const double log_mu_n = log_mu(p, N - 1);
-  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
-  const double lam_max = serv_rate(p, N) * (1.0 - kEpsilon);
-
-  auto eval = [&](double lam) { return eval_model_compact(p, cum, log_mu_n, lam); };
-  auto eval_ttft = [&](double lam) { return eval_ttft_of(p, eval(lam)); };
-  auto eval_itl = [&](double lam) { return eval_itl_of(p, eval(lam)); };
-
-  double lam_ttft = lam_max;
-  if (pr[P_TARGET_TTFT] > 0.0) {
-    if (binary_search_host(lam_min, lam_max, pr[P_TARGET_TTFT], eval_ttft, &lam_ttft) < 0)
-      return;  // target below the bounded region: infeasible
-  }
-  double lam_itl = lam_max;
-  if (pr[P_TARGET_ITL] > 0.0) {
-    if (binary_search_host(lam_min, lam_max, pr[P_TARGET_ITL], eval_itl, &lam_itl) < 0)
-      return;
-  }
-  double lam_tps = lam_max;
-  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
-
-  double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
-  Stats st = eval(lam);
-  const double rate_star = st.throughput * 1000.0;  // req/s
-
-  const double total_rate = pr[P_TOTAL_RATE];
-  double n_rep = ceil(total_rate / rate_star);
-  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
-  if (n_rep < min_rep) n_rep = min_rep;
-  if (!(n_rep > 0.0)) return;  // as in solve_one
-  const double rate = total_rate / n_rep;  // req/s per replica
-  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
-
-  Stats fin = eval(rate / 1000.0);
-  double rho = fin.n_serv / (double)N;
-  if (rho < 0.0) rho = 0.0;
-  if (rho > 1.0) rho = 1.0;
-
-  out[R_FEASIBLE] = 1.0;
-  out[R_REPLICAS] = n_rep;
-  out[R_RATE_STAR] = rate_star;
-  out[R_ITL] = eval_itl_of(p, fin);
-  out[R_TTFT] = eval_ttft_of(p, fin);
-  out[R_RHO] = rho;
-}
-
-// Table length solve_one_compact needs for a row: trunc(N), 0 if invalid.
-inline int row_compact_length(const double *pr) {
-  return row_valid(pr) ? (int)pr[P_MAX_BATCH] : 0;
+  return longest;
 }
 
 }  // namespace wva

@@ -22,10 +22,13 @@
 //     (the midpoints are bitwise the sequential iterates) and consumes
 //     two bisection levels; wave sync is group-local LDS mailboxes with a
 //     watchdog — no workgroup barriers after the scan;
-//   - every body starts with the row guard (row_rejected): a row that
-//     breaks the contract of queue_core.h, or whose chain exceeds the
-//     max_k this launch reserved, gets the all-zero row before LDS is
-//     touched;
+//   - every body starts the same way: threads 0..5 zero the result row,
+//     then the row guard (row_rejected) ends the workgroup for a row that
+//     breaks the contract of queue_core.h, or whose table exceeds what this
+//     launch reserved, before LDS is touched; the same six threads write a
+//     feasible row's values at the end;
+//   - the solve itself is queue_core.h's (search_targets, row_tail), shared
+//     with the host: a body only decides which threads evaluate what;
 //   - a launch may carry one service-time cs^2 per row (M/G/1 correction,
 //     queue_core.h): it scales the wait inside eval_ttft_of and nowhere
 //     else, so every body and both searches pick it up through Parms;
@@ -56,8 +59,9 @@ namespace wva {
 //   - 384 (speculative-tree multisection, depth 2 — the default for
 //     underfilled, latency-bound launches);
 //   - 896 (depth-3 speculation; measured slower than depth 2).
-// The launcher auto-selects (occupancy-aware, see wva_launch_solve);
-// WVA_GPU_THREADS=64|128|256|384|896 overrides, read per launch.
+// The launcher auto-selects (occupancy-aware, see wva_launch_solve_scv);
+// WVA_GPU_THREADS=64|128|256|384|896 overrides, read per launch.  A sixth
+// kernel runs the 256 body over the compact table (N doubles, not 11*N).
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -93,18 +97,80 @@ __device__ inline int wave_lower_bound(int lo, int hi, int lane, Pred pred) {
   return lo + __ffsll((long long)mask) - 1;
 }
 
-template <int THREADS>
+// Table policies: what a workgroup keeps in LDS for its row.  A policy
+// supplies the row guard's length test, the number of states build_cum
+// scans, log_p(n), and the geometric tail with the sweep bound that goes
+// with it.  Each takes the tail's d its own way (the difference of two table
+// entries, or log(lam) - L_N directly) and has its own g_start / loop_hi
+// rule; the two are not numerically interchangeable.
+
+// cum[0..K-1], K = 11 * N; the launch reserves max_k doubles
+struct LdsFullTable {
+  const double *cum;
+  int K;
+  static __device__ bool fits(const double *pr, int max_k) {
+    return row_chain_length(pr) <= max_k;
+  }
+  __device__ LdsFullTable(const Parms &p, const double *table)
+      : cum(table), K(p.max_batch * (1 + kMaxQueueToBatchRatio)) {}
+  __device__ int scan_length() const { return K; }
+  __device__ int chain() const { return K; }
+  __device__ double log_p(double loglam, int n) const { return wva::log_p(cum, loglam, n); }
+  // closed-form sum of the states past N, up to 10/11 of the chain — the
+  // per-state exp calls they would cost are the kernel's dominant fp64 work
+  __device__ GeoTail tail(int num, double loglam, double m, int *loop_hi) const {
+    const int g_start = num + 1;
+    GeoTail t{0.0, 0.0, 0.0, false};
+    *loop_hi = K;
+    if (g_start + 8 <= K) {
+      const double d = loglam - (cum[g_start] - cum[g_start - 1]);
+      t = geo_tail(log_p(loglam, g_start) - m, d, g_start, K, K);
+      if (t.used) *loop_hi = g_start - 1;
+    }
+    return t;
+  }
+};
+
+// cum[0..N-1] only (queue_core.h, "Compact table"); the launch reserves
+// max_n doubles.  The sweep over the N+1 pre-batch states reads cum[n-1]
+// with n-1 <= N-1, the mode is at most N-1 or K, and log_p(N+1), log_p(K)
+// and the tail's increment are closed form in L_N = log(serv_rate(N)).
+struct LdsCompactTable {
+  const double *cum;
+  int N;
+  double log_mu_n;  // L_N
+  // the compare is on the double, so an N no int holds is rejected by
+  // row_valid before any cast
+  static __device__ bool fits(const double *pr, int max_n) {
+    return trunc(pr[P_MAX_BATCH]) <= (double)max_n;
+  }
+  __device__ LdsCompactTable(const Parms &p, const double *table)
+      : cum(table), N(p.max_batch), log_mu_n(log_mu(p, p.max_batch - 1)) {}
+  __device__ int scan_length() const { return N; }
+  __device__ int chain() const { return N * (1 + kMaxQueueToBatchRatio); }
+  __device__ double log_p(double loglam, int n) const {
+    return log_p_compact(cum, N, log_mu_n, loglam, n);
+  }
+  __device__ GeoTail tail(int, double loglam, double m, int *loop_hi) const {
+    return geo_tail_compact(cum, N, log_mu_n, loglam, m, loop_hi);
+  }
+};
+
+// One model evaluation by THREADS threads over a table in LDS.  With one
+// wave (THREADS == 64) it is barrier-free and indexed by the LANE, so the
+// waves of the dual and speculative kernels each run their own; with more
+// it takes two workgroup barriers, which every thread must reach.
+template <int THREADS, typename Table>
 struct WgEval {
   static constexpr int WAVES = THREADS / 64;
   const Parms &p;
-  const double *cum;  // LDS, K entries
-  double *red;        // LDS scratch
-  int K;
+  Table table;
+  double *red;  // LDS scratch, WAVES * 5 (unused with one wave)
 
-  // Wave-parallel equivalents of log_mode_state/state_window
-  // (queue_core.h): same boundary indices, found with ballots instead of
-  // per-lane serial bisections.
-  __device__ int mode_state_wave(double lam, int lane) const {
+  // Wave-parallel equivalent of log_mode_state (queue_core.h): same
+  // boundary index, found with ballots instead of a per-lane serial
+  // bisection.
+  __device__ int mode_state_wave(int K, double lam, int lane) const {
     double tN = prefill_time(p, (double)p.max_batch) +
                 p.num_decode * decode_time(p, (double)p.max_batch);
     if ((double)p.max_batch <= lam * tN) return K;
@@ -119,8 +185,7 @@ struct WgEval {
     const int tid = threadIdx.x;
     const int wave = tid >> 6;
     const int lane = tid & 63;
-    (void)wave;
-    (void)lane;
+    const int K = table.chain();
     const double loglam = log(lam);
 
     // max of logp via the concavity closed form — wave-parallel
@@ -131,41 +196,25 @@ struct WgEval {
     // closed form below — so the two window boundary searches the
     // windowed design needed are gone entirely.
     int n_star;
-    double m;
     if constexpr (WAVES == 1) {
-      n_star = mode_state_wave(lam, lane);
+      n_star = mode_state_wave(K, lam, lane);
     } else {
       n_star = log_mode_state(p, K, lam);
     }
-    m = log_p(cum, loglam, n_star);
+    double m = table.log_p(loglam, n_star);
     if (m < 0.0) m = 0.0;
-    const int n_lo = 0;
-    const int n_hi = K;
     if constexpr (WAVES > 1) {
       __syncthreads();  // red may still be read from a previous eval
     }
 
-    // single windowed pass: normalization and moment sums (eK is the
-    // state-K boundary term, reduced like the sums — only its owner
-    // thread contributes a non-zero partial).  For WAVES == 1 the index
-    // is the LANE, not the block thread id: that makes WgEval<64> usable
-    // per-wave inside the 128-thread dual kernel (each wave sweeps its
-    // own full window in lockstep, reductions stay wave-local).
+    // single pass: normalization and moment sums (eK is the state-K
+    // boundary term, reduced like the sums — only its owner thread
+    // contributes a non-zero partial).  The geometric tail is uniform
+    // across lanes and joins the reduced totals below.
     const int num = p.max_batch;
     const int idx = (WAVES == 1) ? lane : tid;
-    // Geometric tail over the constant-service-rate queue region
-    // (queue_core.h geo_tail): closed-form sum of the states past N,
-    // which are up to 10/11 of the window — the per-state exp calls
-    // they would cost are the kernel's dominant fp64 work.  Uniform
-    // across lanes; added to the reduced totals below.
-    const int g_start = (num + 1 > n_lo) ? num + 1 : n_lo;
-    GeoTail tail{0.0, 0.0, 0.0, false};
-    int loop_hi = n_hi;
-    if (g_start + 8 <= n_hi) {
-      const double d = loglam - (cum[g_start] - cum[g_start - 1]);
-      tail = geo_tail(cum, loglam, d, m, g_start, n_hi, K);
-      if (tail.used) loop_hi = g_start - 1;
-    }
+    int loop_hi;
+    const GeoTail tail = table.tail(num, loglam, m, &loop_hi);
     double S = 0.0, Ni = 0.0, Snum = 0.0, Ninum = 0.0, eK = 0.0;
     // 2x-unrolled sweep: two independent exp chains in flight per lane
     // hide the fp64 transcendental latency the PMC profile flagged
@@ -174,11 +223,11 @@ struct WgEval {
     // covered by the cross-geometry ulp-tolerance in the parity suite.
     {
       double S1 = 0.0, Ni1 = 0.0, Snum1 = 0.0, Ninum1 = 0.0, eK1 = 0.0;
-      int n = n_lo + idx;
+      int n = idx;
       for (; n + THREADS <= loop_hi; n += 2 * THREADS) {
         const int n2 = n + THREADS;
-        const double e = exp(log_p(cum, loglam, n) - m);
-        const double e2 = exp(log_p(cum, loglam, n2) - m);
+        const double e = exp(table.log_p(loglam, n) - m);
+        const double e2 = exp(table.log_p(loglam, n2) - m);
         S += e;
         Ni += (double)n * e;
         S1 += e2;
@@ -195,7 +244,7 @@ struct WgEval {
         if (n2 == K) eK1 = e2;
       }
       if (n <= loop_hi) {
-        const double e = exp(log_p(cum, loglam, n) - m);
+        const double e = exp(table.log_p(loglam, n) - m);
         S += e;
         Ni += (double)n * e;
         if (n <= num) {
@@ -242,33 +291,114 @@ struct WgEval {
         eK += red[w * 5 + 4];
       }
     }
-    // geometric tail joins after the reduction (uniform on all lanes)
     S += tail.S;
     Ni += tail.Ni;
     eK += tail.eK;
-
-    Stats st;
-    st.throughput = lam * (1.0 - eK / S);
-    double n_sys = Ni / S;
-    st.n_serv = Ninum / S + (1.0 - Snum / S) * (double)num;
-    if (st.throughput == 0.0) {
-      st.wait = st.serv = 0.0;
-    } else {
-      double resp = n_sys / st.throughput;
-      st.serv = st.n_serv / st.throughput;
-      st.wait = resp - st.serv;
-      if (st.wait < 0.0) st.wait = 0.0;
-    }
-    return st;
+    return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
   }
-
-  __device__ double eval_ttft(double lam) const { return eval_ttft_of(p, eval(lam)); }
-  __device__ double eval_itl(double lam) const { return eval_itl_of(p, eval(lam)); }
 };
 
-// Uniform-control-flow bisection (all threads run it in lockstep; the eval
-// results are identical on every thread because they come from broadcast
-// reductions).  Semantics mirror analyzer/search.py.
+// The row's cs^2: the launch's optional vector, indexed by the workgroup's
+// row; a launch without one is Markovian (1.0), so stale bytes behind a
+// reused buffer are never read.
+__device__ inline double row_scv(const double *scv, int pid) {
+  return scv != nullptr ? scv[pid] : 1.0;
+}
+
+// Row guard of every body, taken before anything touches LDS: true for a
+// row that breaks the contract of queue_core.h (row_valid, which also wants
+// the row's cs^2 finite and >= 0), or whose table does not fit the doubles
+// this launch reserved for it.  Every thread of the workgroup reads the same
+// row, so the early return it decides is uniform and precedes the first
+// barrier.
+template <typename Table>
+__device__ inline bool row_rejected(const double *pr, double scv, int reserved) {
+  return !(row_valid(pr, scv) & Table::fits(pr, reserved));
+}
+
+// Result stores.  Threads 0..RESULT_FIELDS-1 zero the row once, first thing
+// in every body, and the same threads write a feasible row's values, one
+// field each: both stores to a field come from one thread, in program
+// order, and every exit in between leaves the all-zero row behind.
+__device__ inline void zero_row(double *res) {
+  if (threadIdx.x < RESULT_FIELDS) res[threadIdx.x] = 0.0;
+}
+
+__device__ inline void store_row(double *res, const RowValues vals) {
+  const int tid = threadIdx.x;
+  if (tid < RESULT_FIELDS) {
+    double v = vals.feasible;
+    v = (tid == R_REPLICAS) ? vals.replicas : v;
+    v = (tid == R_RATE_STAR) ? vals.rate_star : v;
+    v = (tid == R_ITL) ? vals.itl : v;
+    v = (tid == R_TTFT) ? vals.ttft : v;
+    v = (tid == R_RHO) ? vals.rho : v;
+    res[tid] = v;
+  }
+}
+
+// chunked parallel inclusive scan of log_mu over K states into LDS
+template <int THREADS>
+__device__ void build_cum(const Parms &p, int K, double *cum, double *totals) {
+  const int tid = threadIdx.x;
+  const int chunk = (K + THREADS - 1) / THREADS;
+  const int lo = tid * chunk;
+  const int hi = min(lo + chunk, K);
+  double acc = 0.0;
+  for (int n = lo; n < hi; ++n) {
+    acc += log_mu(p, n);
+    cum[n] = acc;
+  }
+  totals[tid] = (lo < K) ? acc : 0.0;
+  __syncthreads();
+  double offset = 0.0;
+  for (int t = 0; t < tid; ++t) offset += totals[t];  // broadcast LDS reads
+  for (int n = lo; n < hi; ++n) cum[n] += offset;
+  __syncthreads();
+}
+
+// Sequential body: the whole workgroup evaluates one rate at a time and runs
+// queue_core.h's solve_row in lockstep — every evaluation result is the same
+// on all threads (broadcast reductions), so each search step, each
+// infeasibility exit and the evaluator's barriers are reached uniformly.
+// `reserved` is the table length the launch reserved LDS for (max_k for the
+// full table, max_n for the compact one).
+// LDS: cum[reserved], totals[THREADS], red[WAVES * 5] of the 64 slack doubles.
+template <int THREADS, typename Table>
+__device__ void solve_body(const double *__restrict__ prob,
+                           const double *__restrict__ scv, double *__restrict__ out,
+                           int n_problems, int reserved) {
+  const int pid = blockIdx.x;
+  if (pid >= n_problems) return;
+  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
+  double *res = out + (size_t)pid * RESULT_FIELDS;
+
+  const double cs2 = row_scv(scv, pid);
+  zero_row(res);
+  if (row_rejected<Table>(pr, cs2, reserved)) return;
+  const Parms p = parms_from_problem(pr, cs2);
+
+  extern __shared__ double smem[];
+  double *cum = smem;                // this problem's table
+  double *totals = smem + reserved;  // THREADS chunk totals
+  double *red = totals + THREADS;
+
+  const Table table(p, cum);
+  build_cum<THREADS>(p, table.scan_length(), cum, totals);
+
+  WgEval<THREADS, Table> ev{p, table, red};
+  store_row(res, solve_row(pr, p, ev));
+}
+
+// The dual body's own bisection: queue_core.h's binary_search with the
+// bracket classification written out and y(x_max) evaluated only after
+// y(x_min) missed the target.  Same results, bit for bit; it is kept apart
+// for speed alone.  Over the shared binary_search the dual kernel compiles
+// to 127 registers instead of 133 and a different schedule, which measured
+// 3-5 % slower at B = 4096, N = 256 (0.4556 against 0.4310 ms) — a shape it
+// is the automatic pick for — though faster at N = 64 and 700.  With this
+// text it matches the earlier kernel at all three (profiles/native_dedup.md).
+// A change to the search has to be made in both.
 template <typename F>
 __device__ int wg_binary_search(double x_min, double x_max, double y_target, F eval,
                                 double *x_star) {
@@ -315,123 +445,10 @@ __device__ int wg_binary_search(double x_min, double x_max, double y_target, F e
   return 0;
 }
 
-// The row's cs^2: the launch's optional vector, indexed by the workgroup's
-// row; a launch without one is Markovian (1.0), so stale bytes behind a
-// reused buffer are never read.
-__device__ inline double row_scv(const double *scv, int pid) {
-  return scv != nullptr ? scv[pid] : 1.0;
-}
-
-// Row guard shared by the three bodies, taken before anything touches
-// LDS: a row that breaks the contract of queue_core.h (row_valid, which
-// also wants the row's cs^2 finite and >= 0), or whose chain does not fit
-// the max_k doubles this launch reserved for cum, gets the all-zero result
-// row.  Every thread of the workgroup reads the same row, so the early
-// return is uniform and precedes the first barrier.
-__device__ inline bool row_rejected(const double *pr, double scv, double *res, int max_k) {
-  const bool ok = row_valid(pr, scv) & (row_chain_length(pr) <= max_k);
-  if (!ok && threadIdx.x < RESULT_FIELDS) res[threadIdx.x] = 0.0;
-  return !ok;
-}
-
-// chunked parallel inclusive scan of log_mu over K states into LDS
-template <int THREADS>
-__device__ void build_cum(const Parms &p, int K, double *cum, double *totals) {
-  const int tid = threadIdx.x;
-  const int chunk = (K + THREADS - 1) / THREADS;
-  const int lo = tid * chunk;
-  const int hi = min(lo + chunk, K);
-  double acc = 0.0;
-  for (int n = lo; n < hi; ++n) {
-    acc += log_mu(p, n);
-    cum[n] = acc;
-  }
-  totals[tid] = (lo < K) ? acc : 0.0;
-  __syncthreads();
-  double offset = 0.0;
-  for (int t = 0; t < tid; ++t) offset += totals[t];  // broadcast LDS reads
-  for (int n = lo; n < hi; ++n) cum[n] += offset;
-  __syncthreads();
-}
-
-template <int THREADS>
-__device__ void solve_body(const double *__restrict__ prob,
-                           const double *__restrict__ scv, double *__restrict__ out,
-                           int n_problems, int max_k) {
-  const int pid = blockIdx.x;
-  if (pid >= n_problems) return;
-  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
-  double *res = out + (size_t)pid * RESULT_FIELDS;
-  const int tid = threadIdx.x;
-
-  const double cs2 = row_scv(scv, pid);
-  if (row_rejected(pr, cs2, res, max_k)) return;
-  const Parms p = parms_from_problem(pr, cs2);
-  const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
-
-  extern __shared__ double smem[];
-  double *cum = smem;             // this problem's K entries
-  double *totals = smem + max_k;  // THREADS chunk totals
-  double *red = totals + THREADS;
-
-  build_cum<THREADS>(p, K, cum, totals);
-
-  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
-  const double lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
-
-  WgEval<THREADS> ev{p, cum, red, K};
-
-  if (tid < RESULT_FIELDS && pid < n_problems) res[tid] = 0.0;
-
-  double lam_ttft = lam_max;
-  if (pr[P_TARGET_TTFT] > 0.0) {
-    int ind = wg_binary_search(
-        lam_min, lam_max, pr[P_TARGET_TTFT],
-        [&](double x) { return ev.eval_ttft(x); }, &lam_ttft);
-    if (ind < 0) return;
-  }
-  double lam_itl = lam_max;
-  if (pr[P_TARGET_ITL] > 0.0) {
-    int ind = wg_binary_search(
-        lam_min, lam_max, pr[P_TARGET_ITL],
-        [&](double x) { return ev.eval_itl(x); }, &lam_itl);
-    if (ind < 0) return;
-  }
-  double lam_tps = lam_max;
-  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
-
-  const double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
-  Stats st = ev.eval(lam);
-  const double rate_star = st.throughput * 1000.0;  // req/s
-
-  const double total_rate = pr[P_TOTAL_RATE];
-  double n_rep = ceil(total_rate / rate_star);
-  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
-  if (n_rep < min_rep) n_rep = min_rep;
-  // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
-  // fails every ordered compare): infeasible, as in queue_host.h
-  if (!(n_rep > 0.0)) return;
-  const double rate = total_rate / n_rep;
-  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
-
-  Stats fin = ev.eval(rate / 1000.0);
-  double rho = fin.n_serv / (double)p.max_batch;
-  rho = fmin(fmax(rho, 0.0), 1.0);
-
-  if (tid == 0) {
-    res[R_FEASIBLE] = 1.0;
-    res[R_REPLICAS] = n_rep;
-    res[R_RATE_STAR] = rate_star;
-    res[R_ITL] = eval_itl_of(p, fin);
-    res[R_TTFT] = eval_ttft_of(p, fin);
-    res[R_RHO] = rho;
-  }
-}
-
 // 2-wave "dual" body: the TTFT and ITL bisections are independent, so
 // wave 0 searches the TTFT target while wave 1 searches the ITL target
-// concurrently.  Each wave's evaluations are the barrier-free WgEval<64>
-// (lane-indexed, __shfl-only), so the waves may diverge arbitrarily
+// concurrently.  Each wave's evaluations are the barrier-free one-wave
+// WgEval (lane-indexed, __shfl-only), so the waves may diverge arbitrarily
 // between the scan barrier and the exchange barrier.  Semantics are
 // identical to the sequential body: the original runs TTFT first and
 // returns infeasible without touching ITL — here both run, but the
@@ -449,23 +466,22 @@ __device__ void solve_body_dual(const double *__restrict__ prob,
   const int wave = tid >> 6;
 
   const double cs2 = row_scv(scv, pid);
-  if (row_rejected(pr, cs2, res, max_k)) return;
+  zero_row(res);
+  if (row_rejected<LdsFullTable>(pr, cs2, max_k)) return;
   const Parms p = parms_from_problem(pr, cs2);
-  const int K = p.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
   double *cum = smem;             // this problem's K entries
   double *totals = smem + max_k;  // THREADS chunk totals
   double *ex = totals + THREADS;  // exchange: lam_ttft, ind_ttft, lam_itl, ind_itl
 
-  build_cum<THREADS>(p, K, cum, totals);
+  const LdsFullTable table(p, cum);
+  build_cum<THREADS>(p, table.scan_length(), cum, totals);
 
-  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
-  const double lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
+  double lam_min, lam_max;
+  rate_bracket(p, &lam_min, &lam_max);
 
-  WgEval<64> ev{p, cum, nullptr, K};  // lane-indexed, barrier-free
-
-  if (tid < RESULT_FIELDS) res[tid] = 0.0;
+  WgEval<64, LdsFullTable> ev{p, table, nullptr};
 
   double lam_t = lam_max;
   int ind = 0;
@@ -473,13 +489,13 @@ __device__ void solve_body_dual(const double *__restrict__ prob,
     if (pr[P_TARGET_TTFT] > 0.0) {
       ind = wg_binary_search(
           lam_min, lam_max, pr[P_TARGET_TTFT],
-          [&](double x) { return ev.eval_ttft(x); }, &lam_t);
+          [&](double x) { return eval_ttft_of(p, ev.eval(x)); }, &lam_t);
     }
   } else {
     if (pr[P_TARGET_ITL] > 0.0) {
       ind = wg_binary_search(
           lam_min, lam_max, pr[P_TARGET_ITL],
-          [&](double x) { return ev.eval_itl(x); }, &lam_t);
+          [&](double x) { return eval_itl_of(p, ev.eval(x)); }, &lam_t);
     }
   }
   if ((tid & 63) == 0) {
@@ -490,35 +506,7 @@ __device__ void solve_body_dual(const double *__restrict__ prob,
   if (ex[1] < 0.0 || ex[3] < 0.0) return;  // a target below the reachable range
   if (wave == 1) return;                   // wave 0 finishes the tail alone
 
-  double lam_tps = lam_max;
-  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
-
-  const double lam = fmin(ex[0], fmin(ex[2], lam_tps));
-  Stats st = ev.eval(lam);
-  const double rate_star = st.throughput * 1000.0;  // req/s
-
-  const double total_rate = pr[P_TOTAL_RATE];
-  double n_rep = ceil(total_rate / rate_star);
-  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
-  if (n_rep < min_rep) n_rep = min_rep;
-  // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
-  // fails every ordered compare): infeasible, as in queue_host.h
-  if (!(n_rep > 0.0)) return;
-  const double rate = total_rate / n_rep;
-  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
-
-  Stats fin = ev.eval(rate / 1000.0);
-  double rho = fin.n_serv / (double)p.max_batch;
-  rho = fmin(fmax(rho, 0.0), 1.0);
-
-  if (tid == 0) {
-    res[R_FEASIBLE] = 1.0;
-    res[R_REPLICAS] = n_rep;
-    res[R_RATE_STAR] = rate_star;
-    res[R_ITL] = eval_itl_of(p, fin);
-    res[R_TTFT] = eval_ttft_of(p, fin);
-    res[R_RHO] = rho;
-  }
+  store_row(res, row_tail(pr, p, ev, lam_max, ex[0], ex[2]));
 }
 
 // ---------------------------------------------------------------------------
@@ -533,7 +521,7 @@ __device__ void solve_body_dual(const double *__restrict__ prob,
 // current bracket concurrently — candidate k (heap order) is the
 // midpoint reached after the D halvings encoded by k's bits, computed by
 // the same (lo+hi)/2 recurrence the sequential loop uses, so the
-// iterates x are BITWISE identical to wg_binary_search's and, over the
+// iterates x are BITWISE identical to binary_search's and, over the
 // same cum table, so is every y and the whole result.  Across geometries
 // the table itself is not the same: build_cum's chunked scan adds log_mu
 // in a THREADS-dependent order once K > 64, which moves y and the
@@ -608,7 +596,8 @@ __device__ inline double heap_midpoint(double lo, double hi, int k) {
 // Speculative bisection for one search group.  All SW waves of the group
 // execute this with identical control flow; `sub` is the wave's index
 // within the group, `yb`/`fl` its SW-slot mailbox.  Returns the boundary
-// indicator (-1/0/+1) and writes lambda* like wg_binary_search.
+// indicator (-1/0/+1) and writes lambda* like binary_search, whose bracket
+// classification it shares (queue_core.h).
 template <int D, typename F>
 __device__ int spec_binary_search(double x_min, double x_max, double y_target,
                                   F eval, int sub, volatile double *yb,
@@ -627,32 +616,9 @@ __device__ int spec_binary_search(double x_min, double x_max, double y_target,
   }
   const double y0 = yb[0];
   const double y1 = yb[1];
-
-  if (within_tolerance(y0, y_target, kTolerance)) {
-    *x_star = x_min;
-    return 0;
-  }
-  if (within_tolerance(y1, y_target, kTolerance)) {
-    *x_star = x_max;
-    return 0;
-  }
-  if (within_tolerance(y0, y1, kTolerance)) {
-    if (y_target > fmax(y0, y1)) {
-      *x_star = x_max;
-      return +1;
-    }
-    *x_star = x_min;
-    return -1;
-  }
-  const bool increasing = y0 < y1;
-  if ((increasing && y_target < y0) || (!increasing && y_target > y0)) {
-    *x_star = x_min;
-    return -1;
-  }
-  if ((increasing && y_target > y1) || (!increasing && y_target < y1)) {
-    *x_star = x_max;
-    return +1;
-  }
+  bool increasing = false;
+  const int cls = classify_bracket(x_min, x_max, y0, y1, y_target, x_star, &increasing);
+  if (cls != kBisect) return cls;
 
   double lo = x_min, hi = x_max, xs = x_min;
   double round_id = 2.0;
@@ -717,9 +683,9 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
   const int lane = tid & 63;
 
   const double cs2 = row_scv(scv, pid);
-  if (row_rejected(pr, cs2, res, max_k)) return;
+  zero_row(res);
+  if (row_rejected<LdsFullTable>(pr, cs2, max_k)) return;
   const Parms p0 = parms_from_problem(pr, cs2);
-  const int K = p0.max_batch * (1 + kMaxQueueToBatchRatio);
 
   extern __shared__ double smem[];
   double *cum = smem;
@@ -739,15 +705,14 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
     pp = shared_parms;
   }
 
-  build_cum<THREADS>(p0, K, cum, totals);  // ends with __syncthreads()
+  const LdsFullTable table(p0, cum);
+  build_cum<THREADS>(p0, table.scan_length(), cum, totals);  // ends with __syncthreads()
   const Parms &p = *pp;
 
-  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
-  const double lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
+  double lam_min, lam_max;
+  rate_bracket(p, &lam_min, &lam_max);
 
-  WgEval<64> ev{p, cum, nullptr, K};  // lane-indexed, barrier-free
-
-  if (tid < RESULT_FIELDS) res[tid] = 0.0;
+  WgEval<64, LdsFullTable> ev{p, table, nullptr};  // lane-indexed, barrier-free
 
   volatile double *yb = mail + group * 14;
   volatile double *fl = yb + 7;
@@ -761,11 +726,11 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
     if (group == 0) {
       ind = spec_binary_search<D>(
           lam_min, lam_max, target,
-          [&](double x) { return ev.eval_ttft(x); }, sub, yb, fl, &lam_t);
+          [&](double x) { return eval_ttft_of(p, ev.eval(x)); }, sub, yb, fl, &lam_t);
     } else {
       ind = spec_binary_search<D>(
           lam_min, lam_max, target,
-          [&](double x) { return ev.eval_itl(x); }, sub, yb, fl, &lam_t);
+          [&](double x) { return eval_itl_of(p, ev.eval(x)); }, sub, yb, fl, &lam_t);
     }
   }
   if (sub == 0 && lane == 0) {
@@ -779,35 +744,7 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
   if (!mb_wait(done, 2, 1.0)) return;  // watchdog: leave result infeasible
   if (ex[1] < 0.0 || ex[3] < 0.0) return;  // a target below reachable range
 
-  double lam_tps = lam_max;
-  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
-
-  const double lam = fmin(ex[0], fmin(ex[2], lam_tps));
-  Stats st = ev.eval(lam);
-  const double rate_star = st.throughput * 1000.0;  // req/s
-
-  const double total_rate = pr[P_TOTAL_RATE];
-  double n_rep = ceil(total_rate / rate_star);
-  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
-  if (n_rep < min_rep) n_rep = min_rep;
-  // no replicas, or a per-replica rate that is not > 0 (NaN from 0/0
-  // fails every ordered compare): infeasible, as in queue_host.h
-  if (!(n_rep > 0.0)) return;
-  const double rate = total_rate / n_rep;
-  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
-
-  Stats fin = ev.eval(rate / 1000.0);
-  double rho = fin.n_serv / (double)p.max_batch;
-  rho = fmin(fmax(rho, 0.0), 1.0);
-
-  if (tid == 0) {
-    res[R_FEASIBLE] = 1.0;
-    res[R_REPLICAS] = n_rep;
-    res[R_RATE_STAR] = rate_star;
-    res[R_ITL] = eval_itl_of(p, fin);
-    res[R_TTFT] = eval_ttft_of(p, fin);
-    res[R_RHO] = rho;
-  }
+  store_row(res, row_tail(pr, p, ev, lam_max, ex[0], ex[2]));
 }
 
 extern "C" __global__ void __launch_bounds__(384) wva_solve_kernel_384(
@@ -825,13 +762,13 @@ extern "C" __global__ void __launch_bounds__(896) wva_solve_kernel_896(
 extern "C" __global__ void __launch_bounds__(256) wva_solve_kernel_256(
     const double *__restrict__ prob, const double *__restrict__ scv,
     double *__restrict__ out, int n_problems, int max_k) {
-  solve_body<256>(prob, scv, out, n_problems, max_k);
+  solve_body<256, LdsFullTable>(prob, scv, out, n_problems, max_k);
 }
 
 extern "C" __global__ void __launch_bounds__(64) wva_solve_kernel_64(
     const double *__restrict__ prob, const double *__restrict__ scv,
     double *__restrict__ out, int n_problems, int max_k) {
-  solve_body<64>(prob, scv, out, n_problems, max_k);
+  solve_body<64, LdsFullTable>(prob, scv, out, n_problems, max_k);
 }
 
 extern "C" __global__ void __launch_bounds__(128) wva_solve_kernel_128(
@@ -840,205 +777,17 @@ extern "C" __global__ void __launch_bounds__(128) wva_solve_kernel_128(
   solve_body_dual(prob, scv, out, n_problems, max_k);
 }
 
-// ---------------------------------------------------------------------------
 // Compact-table kernel: rows with max batch beyond the full table's LDS
-// limit (N up to ~7800 instead of ~700).
-//
-// LDS holds cum[0..N-1] only (queue_core.h, "Compact table"): the sweep
-// over the N+1 pre-batch states reads cum[n-1] with n-1 <= N-1, the mode is
-// at most N-1 or K, and log_p(N+1), log_p(K) and the geometric tail's
-// increment are closed form in L_N = log(serv_rate(N)).  One geometry: 256
-// threads, modelled on solve_body<256> — build_cum over N states, scalar
-// mode search, 4-wave strided 2x-unrolled sweeps (consecutive lanes on
-// consecutive doubles) with the LDS cross-wave combine, sequential TTFT then
-// ITL bisection.  Workgroup barriers only; control flow is uniform because
-// every evaluation result is the same on all threads.
-// LDS: (max_n + 256 + 64) doubles.
-// ---------------------------------------------------------------------------
+// limit (N up to ~7800 instead of ~700).  One geometry: the sequential body
+// at 256 threads over LdsCompactTable — build_cum over N states, scalar mode
+// search, 4-wave strided sweeps with the LDS cross-wave combine, TTFT then
+// ITL bisection.  LDS: (max_n + 256 + 64) doubles.
 constexpr int kCompactThreads = 256;
-
-struct WgEvalCompact {
-  static constexpr int THREADS = kCompactThreads;
-  static constexpr int WAVES = THREADS / 64;
-  const Parms &p;
-  const double *cum;  // LDS, N entries
-  double *red;        // LDS scratch, WAVES * 5
-  double log_mu_n;    // L_N
-
-  __device__ Stats eval(double lam) const {
-    const int tid = threadIdx.x;
-    const int wave = tid >> 6;
-    const int lane = tid & 63;
-    const int num = p.max_batch;
-    const int K = num * (1 + kMaxQueueToBatchRatio);
-    const double loglam = log(lam);
-
-    const int n_star = log_mode_state(p, K, lam);
-    double m = log_p_compact(cum, num, log_mu_n, loglam, n_star);
-    if (m < 0.0) m = 0.0;
-    __syncthreads();  // red may still be read from a previous eval
-
-    // queue region (N, K] in closed form; uniform across lanes
-    const int g_start = num + 1;
-    const double d = loglam - log_mu_n;
-    const GeoTail tail = geo_tail_at(
-        log_p_compact(cum, num, log_mu_n, loglam, g_start) - m, d, g_start, K, K);
-    const int loop_hi = tail.used ? num : K;
-
-    // 2x-unrolled strided sweep, two independent exp chains per lane
-    double S = 0.0, Ni = 0.0, Snum = 0.0, Ninum = 0.0, eK = 0.0;
-    {
-      double S1 = 0.0, Ni1 = 0.0, Snum1 = 0.0, Ninum1 = 0.0, eK1 = 0.0;
-      int n = tid;
-      for (; n + THREADS <= loop_hi; n += 2 * THREADS) {
-        const int n2 = n + THREADS;
-        const double e = exp(log_p_compact(cum, num, log_mu_n, loglam, n) - m);
-        const double e2 = exp(log_p_compact(cum, num, log_mu_n, loglam, n2) - m);
-        S += e;
-        Ni += (double)n * e;
-        S1 += e2;
-        Ni1 += (double)n2 * e2;
-        if (n <= num) {
-          Snum += e;
-          Ninum += (double)n * e;
-        }
-        if (n2 <= num) {
-          Snum1 += e2;
-          Ninum1 += (double)n2 * e2;
-        }
-        if (n == K) eK = e;
-        if (n2 == K) eK1 = e2;
-      }
-      if (n <= loop_hi) {
-        const double e = exp(log_p_compact(cum, num, log_mu_n, loglam, n) - m);
-        S += e;
-        Ni += (double)n * e;
-        if (n <= num) {
-          Snum += e;
-          Ninum += (double)n * e;
-        }
-        if (n == K) eK = e;
-      }
-      S += S1;
-      Ni += Ni1;
-      Snum += Snum1;
-      Ninum += Ninum1;
-      eK += eK1;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      S += __shfl_down(S, off, 64);
-      Ni += __shfl_down(Ni, off, 64);
-      Snum += __shfl_down(Snum, off, 64);
-      Ninum += __shfl_down(Ninum, off, 64);
-      eK += __shfl_down(eK, off, 64);
-    }
-    if (lane == 0) {
-      red[wave * 5 + 0] = S;
-      red[wave * 5 + 1] = Ni;
-      red[wave * 5 + 2] = Snum;
-      red[wave * 5 + 3] = Ninum;
-      red[wave * 5 + 4] = eK;
-    }
-    __syncthreads();
-    S = Ni = Snum = Ninum = eK = 0.0;
-    for (int w = 0; w < WAVES; ++w) {
-      S += red[w * 5 + 0];
-      Ni += red[w * 5 + 1];
-      Snum += red[w * 5 + 2];
-      Ninum += red[w * 5 + 3];
-      eK += red[w * 5 + 4];
-    }
-    S += tail.S;
-    Ni += tail.Ni;
-    eK += tail.eK;
-    return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
-  }
-
-  __device__ double eval_ttft(double lam) const { return eval_ttft_of(p, eval(lam)); }
-  __device__ double eval_itl(double lam) const { return eval_itl_of(p, eval(lam)); }
-};
-
-__device__ void solve_body_compact(const double *__restrict__ prob,
-                                   const double *__restrict__ scv,
-                                   double *__restrict__ out, int n_problems, int max_n) {
-  constexpr int THREADS = kCompactThreads;
-  const int pid = blockIdx.x;
-  if (pid >= n_problems) return;
-  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
-  double *res = out + (size_t)pid * RESULT_FIELDS;
-  const int tid = threadIdx.x;
-
-  // Row guard, before LDS is touched: the contract of queue_core.h and a
-  // table of trunc(N) <= max_n doubles.  The compare is on the double, so
-  // an N no int holds is rejected by row_valid before any cast.  The whole
-  // row is zeroed here; a valid row's six fields are overwritten at the end.
-  const double cs2 = row_scv(scv, pid);
-  const bool ok = row_valid(pr, cs2) & (trunc(pr[P_MAX_BATCH]) <= (double)max_n);
-  if (tid < RESULT_FIELDS) res[tid] = 0.0;
-  if (!ok) return;  // uniform: every thread reads the same row
-  const Parms p = parms_from_problem(pr, cs2);
-  const int N = p.max_batch;
-
-  extern __shared__ double smem[];
-  double *cum = smem;             // this problem's N entries
-  double *totals = smem + max_n;  // THREADS chunk totals
-  double *red = totals + THREADS;
-
-  build_cum<THREADS>(p, N, cum, totals);
-
-  const double lam_min = serv_rate(p, 1) * kEpsilon;  // req/ms
-  const double lam_max = serv_rate(p, N) * (1.0 - kEpsilon);
-
-  WgEvalCompact ev{p, cum, red, log_mu(p, N - 1)};
-
-  double lam_ttft = lam_max;
-  if (pr[P_TARGET_TTFT] > 0.0) {
-    int ind = wg_binary_search(
-        lam_min, lam_max, pr[P_TARGET_TTFT],
-        [&](double x) { return ev.eval_ttft(x); }, &lam_ttft);
-    if (ind < 0) return;
-  }
-  double lam_itl = lam_max;
-  if (pr[P_TARGET_ITL] > 0.0) {
-    int ind = wg_binary_search(
-        lam_min, lam_max, pr[P_TARGET_ITL],
-        [&](double x) { return ev.eval_itl(x); }, &lam_itl);
-    if (ind < 0) return;
-  }
-  double lam_tps = lam_max;
-  if (pr[P_TARGET_TPS] > 0.0) lam_tps = lam_max * (1.0 - kStabilityFraction);
-
-  const double lam = fmin(lam_ttft, fmin(lam_itl, lam_tps));
-  Stats st = ev.eval(lam);
-  const double rate_star = st.throughput * 1000.0;  // req/s
-
-  const double total_rate = pr[P_TOTAL_RATE];
-  double n_rep = ceil(total_rate / rate_star);
-  const double min_rep = trunc(pr[P_MIN_REPLICAS]);
-  if (n_rep < min_rep) n_rep = min_rep;
-  if (!(n_rep > 0.0)) return;  // as in queue_host.h
-  const double rate = total_rate / n_rep;
-  if (!(rate > 0.0) || rate > lam_max * 1000.0) return;
-
-  Stats fin = ev.eval(rate / 1000.0);
-  double rho = fin.n_serv / (double)N;
-  rho = fmin(fmax(rho, 0.0), 1.0);
-
-  // the same thread range that zeroed the row writes it, so the two stores
-  // to a field come from one thread, in program order
-  if (tid < RESULT_FIELDS) {
-    const double vals[RESULT_FIELDS] = {1.0, n_rep, rate_star, eval_itl_of(p, fin),
-                                        eval_ttft_of(p, fin), rho};
-    double v = vals[0];
-    for (int f = 1; f < RESULT_FIELDS; ++f) v = (tid == f) ? vals[f] : v;
-    res[tid] = v;
-  }
-}
 
 extern "C" __global__ void __launch_bounds__(kCompactThreads) wva_solve_kernel_compact(
     const double *__restrict__ prob, const double *__restrict__ scv,
     double *__restrict__ out, int n_problems, int max_n) {
-  solve_body_compact(prob, scv, out, n_problems, max_n);
+  solve_body<kCompactThreads, LdsCompactTable>(prob, scv, out, n_problems, max_n);
 }
 
 }  // namespace wva
@@ -1046,91 +795,84 @@ extern "C" __global__ void __launch_bounds__(kCompactThreads) wva_solve_kernel_c
 #include <cstdlib>
 #include <cstring>
 
-// Returns 0 on success, -1 when the selected geometry's LDS footprint
-// (cum[max_k] + totals[threads] + 64 slack doubles) exceeds 64 KiB — decided
-// BEFORE anything is launched — or the hipError_t of a failed launch.
-// scv is the optional device vector of per-row service-time cs^2 (n_problems
-// doubles); nullptr launches the Markovian model.  It changes neither the
-// geometry pick nor the LDS size.
-extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, double *out,
-                                    int n_problems, int max_k, void *stream) {
-  // Geometry auto-selects on state-chain length (measured:
-  // profiles/r01_queue_solver.md, profiles/r01_kernel_sweep.json).  The
-  // 2-wave dual kernel overlaps the TTFT and ITL bisections and is the
-  // default below the large-K regime; the 4-wave kernel's sweep
-  // parallelism takes over for long chains.  WVA_GPU_THREADS=64|128|256
-  // overrides (64 = the sequential single-wave kernel).
-  const char *env = std::getenv("WVA_GPU_THREADS");
+namespace {
+
+using SizingKernel = void (*)(const double *, const double *, double *, int, int);
+
+struct Geometry {
   int threads;
-  // 64 KiB LDS per workgroup: cum[max_k] + totals[threads] + 64 slack
-  const int lds_doubles = 64 * 1024 / 8;
-  auto fits = [&](int thr) { return max_k + thr + 64 <= lds_doubles; };
-  if (env != nullptr && std::strcmp(env, "896") == 0 && fits(896)) {
-    threads = 896;
-  } else if (env != nullptr && std::strcmp(env, "384") == 0 && fits(384)) {
-    threads = 384;
-  } else if (env != nullptr && std::strcmp(env, "256") == 0) {
-    threads = 256;
-  } else if (env != nullptr && std::strcmp(env, "128") == 0) {
-    threads = 128;
-  } else if (env != nullptr && std::strcmp(env, "64") == 0) {
-    threads = 64;
-  } else if (n_problems >= 512) {
-    // Chip-filling launches are THROUGHPUT-bound: with the geometric
-    // queue-tail (queue_core.h geo_tail) collapsing the sweep cost, the
-    // dual kernel's 2 evaluations per round are the least redundant
-    // work at every measured chip-filling point — B=4096 rows of
-    // profiles/r02_kernel_geo.json: 0.33/0.44/1.04 ms at
-    // K=704/2816/7700 vs spec-384's 0.75/1.01/1.21.
-    threads = 128;
-  } else {
-    // Underfilled launches can't occupy 256 CUs, so the serial
-    // bisection IS the runtime and the speculative-tree multisection
-    // kernel (depth 2, 2 x 3 waves, 2 levels per round) wins every
-    // measured point: 0.106/0.116/0.141 ms at B=192 K=704/2816/7700
-    // (r01 best geometry: 0.175/0.277/0.360; profiles/r02_kernel_geo.json).
-    threads = fits(384) ? 384 : 256;
-  }
-  // a forced 64/128/256 or the auto pick may still not fit (N > ~715):
-  // refuse here instead of issuing a launch that cannot start
-  if (max_k < 1 || !fits(threads)) return -1;
-  const size_t smem = (size_t)(max_k + threads + 64) * sizeof(double);
-  if (threads == 64) {
-    hipLaunchKernelGGL(wva::wva_solve_kernel_64, dim3(n_problems), dim3(64), smem,
-                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
-  } else if (threads == 128) {
-    hipLaunchKernelGGL(wva::wva_solve_kernel_128, dim3(n_problems), dim3(128), smem,
-                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
-  } else if (threads == 384) {
-    hipLaunchKernelGGL(wva::wva_solve_kernel_384, dim3(n_problems), dim3(384), smem,
-                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
-  } else if (threads == 896) {
-    hipLaunchKernelGGL(wva::wva_solve_kernel_896, dim3(n_problems), dim3(896), smem,
-                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
-  } else {
-    hipLaunchKernelGGL(wva::wva_solve_kernel_256, dim3(n_problems), dim3(256), smem,
-                       (hipStream_t)stream, prob, scv, out, n_problems, max_k);
-  }
+  const char *name;  // the value of WVA_GPU_THREADS that forces it
+  SizingKernel kernel;
+};
+
+enum { kSeq64, kDual128, kSeq256, kSpec384, kSpec896 };  // rows of kGeometries
+
+const Geometry kGeometries[] = {
+    {64, "64", wva::wva_solve_kernel_64},    {128, "128", wva::wva_solve_kernel_128},
+    {256, "256", wva::wva_solve_kernel_256}, {384, "384", wva::wva_solve_kernel_384},
+    {896, "896", wva::wva_solve_kernel_896},
+};
+
+// 64 KiB LDS per workgroup: the table, totals[threads] and 64 slack doubles
+// (compared so that no table_len can overflow the sum)
+bool fits_lds(int table_len, int threads) {
+  return table_len <= 64 * 1024 / 8 - threads - 64;
+}
+
+// Returns 0 on success, -1 when the table is empty or the LDS footprint
+// exceeds 64 KiB — decided BEFORE anything is launched, instead of issuing a
+// launch that cannot start — or the hipError_t of a failed launch.
+int launch(const Geometry &g, const double *prob, const double *scv, double *out,
+           int n_problems, int table_len, void *stream) {
+  if (table_len < 1 || !fits_lds(table_len, g.threads)) return -1;
+  const size_t smem = (size_t)(table_len + g.threads + 64) * sizeof(double);
+  hipLaunchKernelGGL(g.kernel, dim3(n_problems), dim3(g.threads), smem, (hipStream_t)stream,
+                     prob, scv, out, n_problems, table_len);
   return (int)hipGetLastError();
 }
 
-extern "C" int wva_launch_solve(const double *prob, double *out, int n_problems,
-                                int max_k, void *stream) {
-  return wva_launch_solve_scv(prob, nullptr, out, n_problems, max_k, stream);
+}  // namespace
+
+// Full-table launch; return values as launch() above (-1 for max_k beyond
+// N ~ 715).  scv is the optional device vector of per-row service-time cs^2
+// (n_problems doubles); nullptr launches the Markovian model.  It changes
+// neither the geometry pick nor the LDS size.
+extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, double *out,
+                                    int n_problems, int max_k, void *stream) {
+  // WVA_GPU_THREADS=64|128|256|384|896 forces a geometry; anything else is
+  // ignored.  A forced speculative geometry (384, 896) that does not fit
+  // falls back to the automatic pick; a forced 64/128/256 that does not fit
+  // is refused by launch().
+  const Geometry *g = nullptr;
+  if (const char *env = std::getenv("WVA_GPU_THREADS")) {
+    for (const Geometry &listed : kGeometries) {
+      if (std::strcmp(env, listed.name) == 0) g = &listed;
+    }
+  }
+  if (g != nullptr && g->threads > 256 && !fits_lds(max_k, g->threads)) g = nullptr;
+  if (g == nullptr) {
+    // The automatic pick, on the launch size (measured:
+    // profiles/r02_kernel_geo.json).
+    //   - Chip-filling launches (B >= 512) are THROUGHPUT-bound: with the
+    //     geometric queue-tail (queue_core.h geo_tail) collapsing the sweep
+    //     cost, the dual kernel's 2 evaluations per round are the least
+    //     redundant work at every measured chip-filling point — B=4096 rows:
+    //     0.33/0.44/1.04 ms at K=704/2816/7700 vs spec-384's 0.75/1.01/1.21.
+    //   - Underfilled launches can't occupy 256 CUs, so the serial bisection
+    //     IS the runtime and the speculative-tree multisection kernel (depth
+    //     2, 2 x 3 waves, 2 levels per round) wins every measured point:
+    //     0.106/0.116/0.141 ms at B=192 K=704/2816/7700 (r01 best geometry:
+    //     0.175/0.277/0.360).
+    g = &kGeometries[n_problems >= 512 ? kDual128 : fits_lds(max_k, 384) ? kSpec384 : kSeq256];
+  }
+  return launch(*g, prob, scv, out, n_problems, max_k, stream);
 }
 
 // Compact-table launch: max_n is the largest trunc(N) the launch reserves
-// LDS for (a row beyond it gets the all-zero row).  Same return values as
-// wva_launch_solve_scv: -1, before anything is launched, when cum[max_n] +
-// totals[256] + 64 slack doubles exceed 64 KiB.  One geometry;
+// LDS for (a row beyond it gets the all-zero row).  One geometry;
 // WVA_GPU_THREADS does not apply.
 extern "C" int wva_launch_solve_compact(const double *prob, const double *scv, double *out,
                                         int n_problems, int max_n, void *stream) {
-  const int lds_doubles = 64 * 1024 / 8;
-  if (max_n < 1 || max_n > lds_doubles - wva::kCompactThreads - 64) return -1;
-  const size_t smem = (size_t)(max_n + wva::kCompactThreads + 64) * sizeof(double);
-  hipLaunchKernelGGL(wva::wva_solve_kernel_compact, dim3(n_problems),
-                     dim3(wva::kCompactThreads), smem, (hipStream_t)stream, prob, scv, out,
-                     n_problems, max_n);
-  return (int)hipGetLastError();
+  const Geometry compact{wva::kCompactThreads, "", wva::wva_solve_kernel_compact};
+  return launch(compact, prob, scv, out, n_problems, max_n, stream);
 }

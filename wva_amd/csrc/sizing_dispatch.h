@@ -13,9 +13,9 @@
 // tensor allocations, the pageable upload and download (each an extra
 // staging pass inside the runtime plus a blocking wait) and the fill
 // kernel on an output the sizing kernel overwrites in full: every kernel
-// body writes all six fields of every row it owns (row_rejected zeroes a
-// rejected row; the bodies zero the row before the searches and thread 0
-// writes the six results at the end), so no memset precedes the launch.
+// body writes all six fields of every row it owns (threads 0..5 zero the
+// row before the row guard and write a feasible row's six results at the
+// end), so no memset precedes the launch.
 //
 // A submit may carry one service-time cs^2 per row (queue_core.h, M/G/1
 // correction).  The vector rides in the slot's input buffers, right behind
@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "queue_core.h"
+#include "scv_arg.h"
 
 extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, double *out,
                                     int n_problems, int max_k, void *stream);
@@ -140,7 +141,16 @@ inline void grow_slot(Slot &s, int64_t rows) {
   s.cap_rows = cap;
 }
 
-inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::none()) {
+// either launcher of queue_solver_hip.hip
+using Launcher = int (*)(const double *prob, const double *scv, double *out, int n_problems,
+                         int table_len, void *stream);
+
+// The one submit.  `launch` gets table_len clamped to an int; when it answers
+// -1 (nothing was launched) the error reads not_fit_head, table_len,
+// not_fit_tail.
+inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t table_len,
+                           const py::object &scv, const char *not_fit_head,
+                           const char *not_fit_tail) {
   if (!py::isinstance<py::array_t<double>>(problems)) {
     throw py::type_error("problems must be a float64 array");
   }
@@ -153,20 +163,7 @@ inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::no
   }
   const int64_t B = problems.shape(0);
   if (B > INT_MAX) throw py::value_error("too many problems for one launch");
-  const double *scv_src = nullptr;
-  if (!scv.is_none()) {
-    if (!py::isinstance<py::array_t<double>>(scv)) {
-      throw py::type_error("scv must be a float64 array");
-    }
-    py::array v = py::reinterpret_borrow<py::array>(scv);
-    if (v.ndim() != 1 || v.shape(0) != B) {
-      throw py::value_error("scv must be [B] = [" + std::to_string(B) + "]");
-    }
-    if (!(v.flags() & py::array::c_style)) {
-      throw py::value_error("scv must be C-contiguous");
-    }
-    scv_src = (const double *)v.data();  // the caller's scv outlives this call
-  }
+  const double *scv_src = scv_data(scv, B);
 
   Pool &P = pool();
   std::lock_guard<std::mutex> lock(P.mu);
@@ -215,18 +212,16 @@ inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::no
   hip_check(hipMemcpyAsync(slot->d_in, slot->h_in, in_doubles * sizeof(double),
                            hipMemcpyHostToDevice, P.stream),
             "hipMemcpyAsync (upload)");
-  const int k = max_k > INT_MAX ? INT_MAX : (max_k < 0 ? 0 : (int)max_k);
+  const int len = table_len > INT_MAX ? INT_MAX : (table_len < 0 ? 0 : (int)table_len);
   const double *d_scv = scv_src != nullptr ? slot->d_in + row_doubles : nullptr;
-  const int status = wva_launch_solve_scv(slot->d_in, d_scv, slot->d_out, (int)B, k,
-                                          (void *)P.stream);
+  const int status =
+      launch(slot->d_in, d_scv, slot->d_out, (int)B, len, (void *)P.stream);
   if (status != 0) {
     // nothing was launched; let the upload finish before the slot's pinned
     // buffer can be overwritten by the next submit
     (void)hipStreamSynchronize(P.stream);
     if (status == -1) {
-      throw std::runtime_error(
-          "no kernel geometry holds a chain of length " + std::to_string(max_k) +
-          " in LDS (max_batch limit ~700); use the CPU path for these problems");
+      throw std::runtime_error(not_fit_head + std::to_string(table_len) + not_fit_tail);
     }
     hip_check((hipError_t)status, "sizing kernel launch");
   }
@@ -245,114 +240,20 @@ inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::no
   return slot->ticket;
 }
 
-// submit through the compact-table kernel (queue_solver_hip.hip): max_n is the
-// largest max batch N the launch reserves LDS for (N doubles, up to ~7800).
-// The same slot pool, stream, staging, argument checks and collect as submit,
-// which is left exactly as it was: this is its body with the other launcher.
+// through the full-table kernels: max_k is the chain length 11 * N reserved
+inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::none()) {
+  return submit_with(
+      wva_launch_solve_scv, problems, max_k, scv, "no kernel geometry holds a chain of length ",
+      " in LDS (max_batch limit ~700); use the CPU path for these problems");
+}
+
+// through the compact-table kernel: max_n is the largest max batch N the
+// launch reserves LDS for (N doubles, up to ~7800)
 inline int64_t submit_compact(py::array problems, int64_t max_n,
                               py::object scv = py::none()) {
-  if (!py::isinstance<py::array_t<double>>(problems)) {
-    throw py::type_error("problems must be a float64 array");
-  }
-  if (problems.ndim() != 2 || problems.shape(1) != PROBLEM_FIELDS) {
-    throw py::value_error("problems must be [B, " +
-                          std::to_string((int)PROBLEM_FIELDS) + "]");
-  }
-  if (!(problems.flags() & py::array::c_style)) {
-    throw py::value_error("problems must be C-contiguous");
-  }
-  const int64_t B = problems.shape(0);
-  if (B > INT_MAX) throw py::value_error("too many problems for one launch");
-  const double *scv_src = nullptr;
-  if (!scv.is_none()) {
-    if (!py::isinstance<py::array_t<double>>(scv)) {
-      throw py::type_error("scv must be a float64 array");
-    }
-    py::array v = py::reinterpret_borrow<py::array>(scv);
-    if (v.ndim() != 1 || v.shape(0) != B) {
-      throw py::value_error("scv must be [B] = [" + std::to_string(B) + "]");
-    }
-    if (!(v.flags() & py::array::c_style)) {
-      throw py::value_error("scv must be C-contiguous");
-    }
-    scv_src = (const double *)v.data();  // the caller's scv outlives this call
-  }
-
-  Pool &P = pool();
-  std::lock_guard<std::mutex> lock(P.mu);
-  if (B == 0) {
-    // nothing to solve: no slot, no GPU call
-    const int64_t ticket = P.next_ticket++;
-    P.empty_tickets.insert(ticket);
-    return ticket;
-  }
-  if (P.device < 0) hip_check(hipGetDevice(&P.device), "hipGetDevice");
-  DeviceGuard guard(P.device);
-  if (P.stream == nullptr) {
-    hip_check(hipStreamCreateWithFlags(&P.stream, hipStreamNonBlocking),
-              "hipStreamCreateWithFlags");
-  }
-
-  Slot *slot = nullptr;
-  for (Slot *s : P.slots) {
-    if (s->state == SlotState::kFree) {
-      slot = s;
-      break;
-    }
-  }
-  if (slot == nullptr) {
-    // every slot is in flight: add one, never wait for a collect
-    Slot *s = new Slot();
-    hipError_t err = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-    if (err != hipSuccess) {
-      delete s;
-      hip_check(err, "hipEventCreateWithFlags");
-    }
-    P.slots.push_back(s);
-    slot = s;
-  }
-  // from here to the event record the slot stays kFree: any throw leaves
-  // it reusable
-  grow_slot(*slot, B);
-
-  const size_t row_doubles = (size_t)B * PROBLEM_FIELDS;
-  const size_t in_doubles = row_doubles + (scv_src != nullptr ? (size_t)B : 0);
-  const size_t out_bytes = (size_t)B * RESULT_FIELDS * sizeof(double);
-  std::memcpy(slot->h_in, problems.data(), row_doubles * sizeof(double));
-  if (scv_src != nullptr) {
-    std::memcpy(slot->h_in + row_doubles, scv_src, (size_t)B * sizeof(double));
-  }
-  hip_check(hipMemcpyAsync(slot->d_in, slot->h_in, in_doubles * sizeof(double),
-                           hipMemcpyHostToDevice, P.stream),
-            "hipMemcpyAsync (upload)");
-  const int n = max_n > INT_MAX ? INT_MAX : (max_n < 0 ? 0 : (int)max_n);
-  const double *d_scv = scv_src != nullptr ? slot->d_in + row_doubles : nullptr;
-  const int status = wva_launch_solve_compact(slot->d_in, d_scv, slot->d_out, (int)B, n,
-                                              (void *)P.stream);
-  if (status != 0) {
-    // nothing was launched; let the upload finish before the slot's pinned
-    // buffer can be overwritten by the next submit
-    (void)hipStreamSynchronize(P.stream);
-    if (status == -1) {
-      throw std::runtime_error(
-          "the compact-table kernel cannot hold " + std::to_string(max_n) +
-          " states in LDS (max_batch limit ~7800); use the CPU path for these problems");
-    }
-    hip_check((hipError_t)status, "sizing kernel launch");
-  }
-  hipError_t err = hipMemcpyAsync(slot->h_out, slot->d_out, out_bytes,
-                                  hipMemcpyDeviceToHost, P.stream);
-  if (err == hipSuccess) err = hipEventRecord(slot->done, P.stream);
-  if (err != hipSuccess) {
-    // the kernel may be running on this slot's buffers: drain the stream
-    // before the slot can be handed out again
-    (void)hipStreamSynchronize(P.stream);
-    hip_check(err, "hipMemcpyAsync (download) / hipEventRecord");
-  }
-  slot->state = SlotState::kInFlight;
-  slot->ticket = P.next_ticket++;
-  slot->rows = B;
-  return slot->ticket;
+  return submit_with(
+      wva_launch_solve_compact, problems, max_n, scv, "the compact-table kernel cannot hold ",
+      " states in LDS (max_batch limit ~7800); use the CPU path for these problems");
 }
 
 inline std::vector<py::ssize_t> result_shape(int64_t rows) {

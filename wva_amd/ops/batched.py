@@ -588,7 +588,7 @@ class LargeNGpuDispatch(NativeGpuDispatch):
 DEFAULT_GPU_CHUNKS = 2
 
 # The launcher picks the chip-filling geometry from this many rows on
-# (wva_launch_solve); a fleet that could reach it is never chunked on the
+# (wva_launch_solve_scv); a fleet that could reach it is never chunked on the
 # GPU, so every chunk runs the geometry the whole batch would have run.
 _GPU_CHUNKING_ROW_BOUND = 512
 
