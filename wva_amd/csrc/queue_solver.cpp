@@ -24,6 +24,9 @@
 // Host scalar solve + bisection shared with the torch-free binding.
 #include "queue_host.h"
 
+// Limited-mode greedy solve, the same wrapper as in the torch-free binding.
+#include "greedy_py.h"
+
 #ifdef WVA_WITH_HIP
 // 0 = launched; -1 = no kernel geometry fits max_k in LDS (nothing was
 // launched); otherwise the hipError_t of the failed launch.  scv: one
@@ -148,6 +151,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
+  // greedy_solve, HAS_GREEDY
+  wva::greedy::bind(m);
 #ifdef WVA_WITH_HIP
   m.def("submit", &wva::dispatch::submit,
         "Enqueue upload, sizing kernel and download for a float64 [B, 12] "

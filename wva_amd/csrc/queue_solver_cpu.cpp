@@ -11,6 +11,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "greedy_py.h"
 #include "queue_host.h"
 #include "scv_arg.h"
 
@@ -61,4 +62,6 @@ PYBIND11_MODULE(_queue_native_cpu, m) {
         py::arg("problems"), py::arg("scv") = py::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
+  // limited-mode greedy solve (greedy_core.h): greedy_solve, HAS_GREEDY
+  wva::greedy::bind(m);
 }

@@ -14,11 +14,20 @@ Ordering invariants preserved exactly:
   (greedy.go:147-163);
 - best-effort policies may scale an allocation's replica count and rescale
   cost/value by the replica factor (greedy.go:208-211,299-310).
+
+solve_greedy runs the solve itself in C++ (csrc/greedy_core.h) when an
+extension carries it: _marshal lays the problem out as flat arrays, the
+binding returns the chosen allocation and the granted replicas per server,
+and _apply sets them, rescaling partial grants in Python floats.  The Python
+functions below are unchanged; they are the fallback and the reference the
+native route is tested against (docs/design/native-greedy.md).
 """
 
 from __future__ import annotations
 
 import math
+import os
+from array import array
 from typing import Dict, List, Optional
 
 from ..config import OptimizerSpec, SaturationPolicy
@@ -69,7 +78,164 @@ def _insort(entries: List[ServerEntry], entry: ServerEntry) -> None:
     entries.insert(lo, entry)
 
 
+_POLICY_CODE = {  # greedy_core.h: Policy
+    SaturationPolicy.NONE: 0,
+    SaturationPolicy.PRIORITY_EXHAUSTIVE: 1,
+    SaturationPolicy.PRIORITY_ROUND_ROBIN: 2,
+    SaturationPolicy.ROUND_ROBIN: 3,
+}
+
+# bounds that keep every integer of the native solve inside int64: with
+# |num_replicas| < 2**31, |units_per_replica| < 2**12 and fewer than 2**18
+# allocations the units ever asked for sum to less than 2**61, and so may
+# the capacities
+_MAX_REPLICAS = 1 << 31
+_MAX_UNITS = 1 << 12
+_MAX_ALLOCATIONS = 1 << 18
+_MAX_CAPACITY = 1 << 61
+
+_UNSET = object()
+_binding_module = _UNSET
+
+
+def _binding():
+    """The native module that carries greedy_solve (the torch-free one
+    first), or None."""
+    global _binding_module
+    if _binding_module is _UNSET:
+        _binding_module = None
+        try:
+            from .. import ops
+        except Exception:  # pragma: no cover - no numpy in the environment
+            return None
+        for mod in (ops._native_cpu, ops._native):
+            if mod is not None and getattr(mod, "HAS_GREEDY", False):
+                _binding_module = mod
+                break
+    return _binding_module
+
+
+def _marshal(system: System):
+    """One pass over the servers: clear their allocations and lay the
+    problem out as the flat arrays of csrc/greedy_core.h.  Returns
+    (array arguments, servers, all candidates, their offsets), or None when the
+    system has to take the Python body: a missing model, a non-finite value,
+    or an integer outside the bounds above."""
+    accelerators = system.accelerators
+    models = system.models
+    type_index: Dict[str, int] = {}
+    for acc in accelerators.values():
+        type_index.setdefault(acc.type, len(type_index))
+    capacity = [0] * len(type_index)
+    for t, count in system.capacity.items():
+        i = type_index.get(t)
+        if i is not None:
+            capacity[i] = count
+
+    priorities: Dict[str, int] = {}  # per service class
+    servers = list(system.servers.values())
+    flat: List[Allocation] = []  # every server's candidates, in order
+    model_of: List[str] = []  # per candidate
+    priority = []
+    offsets = [0]
+    for server in servers:
+        server.remove_allocation()
+        allocs = server.all_allocations
+        if allocs:
+            model_name = server.model_name
+            if model_name not in models:
+                return None
+            class_name = server.service_class_name
+            prio = priorities.get(class_name)
+            if prio is None:
+                prio = priorities[class_name] = server.priority(system)
+            priority.append(prio)
+            flat += allocs.values()
+            model_of += [model_name] * len(allocs)
+        else:
+            priority.append(0)
+        offsets.append(len(flat))
+
+    values = [a.value for a in flat]
+    replicas = [a.num_replicas for a in flat]
+    names = [a.accelerator for a in flat]
+    # accelerator type and units per replica, resolved once per accelerator
+    # and once per (model, accelerator)
+    type_of: Dict[str, int] = {}
+    for name in set(names):
+        acc = accelerators.get(name)
+        type_of[name] = -1 if acc is None else type_index[acc.type]
+    pairs = list(zip(model_of, names))
+    units_of: Dict[tuple, int] = {}
+    for pair in set(pairs):
+        acc = accelerators.get(pair[1])
+        units_of[pair] = (
+            0 if acc is None else models[pair[0]].get_num_instances(pair[1]) * acc.multiplicity
+        )
+    types = [type_of[name] for name in names]
+    units = [units_of[pair] for pair in pairs]
+
+    if len(values) >= _MAX_ALLOCATIONS:
+        return None
+    try:
+        if values:
+            if not math.isfinite(sum(values)):  # a NaN or an infinity, or a sum that overflows
+                return None
+            if not (-_MAX_REPLICAS < min(replicas) and max(replicas) < _MAX_REPLICAS):
+                return None
+            resolved = units_of.values()
+            if not (-_MAX_UNITS < min(resolved) and max(resolved) < _MAX_UNITS):
+                return None
+        if sum(map(abs, capacity)) >= _MAX_CAPACITY:
+            return None
+        # 'q' and 'i' take nothing but integers that fit; 'd' takes numbers
+        args = (
+            array("q", capacity), array("q", priority), array("q", offsets),
+            array("d", values), array("q", replicas), array("i", types),
+            array("q", units),
+        )
+    except (TypeError, OverflowError):
+        return None
+    return args, servers, flat, offsets
+
+
+def _apply(servers, flat, offsets, chosen: List[int], granted: List[int]) -> None:
+    """Set what the native solve chose; a partial grant is rescaled here, in
+    Python floats, exactly as _allocate_maximally and _allocate_equally do."""
+    for server, first, index, count in zip(servers, offsets, chosen, granted):
+        if index < 0:
+            continue
+        alloc = flat[first + index]
+        cur = alloc.num_replicas
+        if count != cur:
+            factor = count / cur
+            alloc.cost *= factor
+            alloc.value *= factor
+            alloc.num_replicas = count
+        server.set_allocation(alloc)
+
+
+def _solve_native(system: System, spec: OptimizerSpec, binding) -> bool:
+    marshalled = _marshal(system)
+    if marshalled is None:
+        return False
+    args, servers, flat, offsets = marshalled
+    chosen, granted = binding.greedy_solve(
+        *args,
+        bool(spec.delayed_best_effort),
+        _POLICY_CODE[SaturationPolicy.parse(spec.saturation_policy)],
+    )
+    _apply(servers, flat, offsets, chosen, granted)
+    return True
+
+
 def solve_greedy(system: System, spec: OptimizerSpec) -> None:
+    # native route (csrc/greedy_core.h); WVA_NATIVE_GREEDY=0 switches it off
+    if os.environ.get("WVA_NATIVE_GREEDY", "1") != "0":
+        binding = _binding()
+        if binding is not None and _solve_native(system, spec, binding):
+            return
+
     available: Dict[str, int] = dict(system.capacity)
 
     entries: List[ServerEntry] = []
