@@ -26,7 +26,9 @@ from .queueanalyzer import (
     ServiceParms,
     TargetPerf,
     TargetRate,
+    configured_ttft_tail,
     effective_concurrency,
+    percentile_ttft_tail,
 )
 
 __all__ = [
@@ -52,6 +54,8 @@ __all__ = [
     "TargetPerf",
     "TargetRate",
     "effective_concurrency",
+    "configured_ttft_tail",
+    "percentile_ttft_tail",
     "MG1Corrector",
     "configured_scv",
     "auto_scv_enabled",

@@ -22,6 +22,9 @@ closures over this instance.
 
 from __future__ import annotations
 
+import logging
+import math
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -115,10 +118,49 @@ class TargetPerf:
     target_ttft: float = 0.0  # queueing + prefill (ms); 0 disables
     target_itl: float = 0.0  # inter-token latency (ms); 0 disables
     target_tps: float = 0.0  # token throughput (tok/s); 0 disables
+    # allowed probability that TTFT exceeds target_ttft (p95: 0.05); 0 sizes
+    # to the mean TTFT; valid values are finite with 0 <= ttft_tail < 1
+    ttft_tail: float = 0.0
 
     def check(self) -> None:
         if self.target_itl < 0 or self.target_ttft < 0 or self.target_tps < 0:
             raise AnalyzerError(f"invalid target data values {self}")
+        if not 0.0 <= self.ttft_tail < 1.0:  # also fails NaN
+            raise AnalyzerError(f"invalid TTFT tail probability {self}")
+
+
+def configured_ttft_tail() -> float:
+    """The fleet's TTFT tail probability from ``WVA_TTFT_PERCENTILE`` (read
+    per call): ``95`` sizes to the p95 TTFT, ``ttft_tail = 0.05``.  Unset is
+    0.0: size to the mean TTFT.  So is a value that is no number in (0, 100)
+    (``0.95``, ``100``, ``p95``), with a warning, logged once per value: the
+    operator asked for a percentile and is not getting one."""
+    raw = os.environ.get("WVA_TTFT_PERCENTILE", "").strip()
+    if not raw:
+        return 0.0
+    try:
+        percentile = float(raw)
+        if percentile < 1.0:  # a fraction, not a percentile: 0.95 is not p0.95
+            raise ValueError(raw)
+        return percentile_ttft_tail(percentile)
+    except ValueError:
+        if raw not in _rejected_percentiles:
+            _rejected_percentiles.add(raw)
+            logging.getLogger("wva_amd.analyzer").warning(
+                "WVA_TTFT_PERCENTILE=%r is not a percentile in [1, 100) such as 95; "
+                "sizing to the MEAN TTFT", raw,
+            )
+        return 0.0
+
+
+_rejected_percentiles: set = set()
+
+
+def percentile_ttft_tail(percentile: float) -> float:
+    """``ttft_tail`` of a TTFT percentile in (0, 100); ValueError outside."""
+    if not 0.0 < percentile < 100.0:
+        raise ValueError(f"TTFT percentile must lie in (0, 100), got {percentile}")
+    return (100.0 - percentile) / 100.0
 
 
 @dataclass(frozen=True)
@@ -222,6 +264,52 @@ class QueueAnalyzer:
         )
         return self.service_parms.decode.decode_time(eff_conc)
 
+    def wait_exceedance(self, request_rate: float, t: float) -> float:
+        """P(W > t): the probability that an accepted arrival at
+        ``request_rate`` (req/s) waits longer than ``t`` ms for a batch slot.
+
+        The direct definition, and the specification of every native
+        implementation (csrc/queue_core.h, "Waiting-time tail"): an accepted
+        arrival sees state n with probability p[n] / (1 - p[K]); with n >= N
+        ahead of it, it waits for j = n - N + 1 departures at the full-batch
+        rate mu_N, an Erlang(j, mu_N) time, so with x = mu_N * t
+
+            P(W > t) = sum_{n=N..K-1} pi_n * sum_{i<j} e^-x x^i / i!.
+
+        ``t <= 0`` gives 1.0, as the TTFT search wants it for a target that
+        prefill alone already misses."""
+        return self._wait_exceedance(request_rate / 1000.0, t)
+
+    def _wait_exceedance(self, lam_per_ms: float, t: float) -> float:
+        m = self._solve(lam_per_ms)
+        if not t > 0:
+            return 1.0
+        N, K = self.max_batch_size, self.model.K
+        if K <= N:
+            return 0.0  # no queue: nobody waits
+        pi = m.p[N:K] / (1.0 - m.p[K])
+        x = float(self.serv_rate[-1]) * t
+        i = np.arange(K - N, dtype=np.float64)
+        log_fact = np.cumsum(np.log(np.maximum(i, 1.0)))
+        erlang = np.cumsum(np.exp(i * math.log(x) - x - log_fact))  # [j - 1]: sum over i < j
+        return float(np.dot(pi, erlang))
+
+    def _eval_ttft_tail(self, target_ttft: float):
+        """lam -> P(TTFT > target_ttft): the waiting time, stretched by the
+        M/G/1 wait scale like the mean, has to fit what prefill leaves."""
+
+        def exceedance(lam_per_ms: float) -> float:
+            m = self._solve(lam_per_ms)
+            eff_conc = effective_concurrency(
+                m.avg_serv_time, self.service_parms, self.request_size, self.max_batch_size
+            )
+            prefill = self.service_parms.prefill.prefill_time(
+                self.request_size.avg_input_tokens, eff_conc
+            )
+            return self._wait_exceedance(lam_per_ms, (target_ttft - prefill) / self._wait_scale)
+
+        return exceedance
+
     # -- public API ---------------------------------------------------------
     def analyze(self, request_rate: float) -> AnalysisMetrics:
         """Evaluate performance metrics at a given request rate (req/s)."""
@@ -273,7 +361,18 @@ class QueueAnalyzer:
         lambda_max = self.rate_range.max / 1000.0
 
         lambda_star_ttft = lambda_max
-        if target_perf.target_ttft > 0:
+        if target_perf.target_ttft > 0 and target_perf.ttft_tail > 0:
+            # percentile target: P(TTFT > target_ttft) against ttft_tail
+            lambda_star_ttft, ind = binary_search(
+                lambda_min, lambda_max, target_perf.ttft_tail,
+                self._eval_ttft_tail(target_perf.target_ttft),
+            )
+            if ind == BelowRegion:
+                raise AnalyzerError(
+                    f"failed to calculate lambdaStarTTFT: P(TTFT > {target_perf.target_ttft}) "
+                    f"exceeds {target_perf.ttft_tail} on the bounded region {self.rate_range}"
+                )
+        elif target_perf.target_ttft > 0:
             lambda_star_ttft, ind = binary_search(
                 lambda_min, lambda_max, target_perf.target_ttft, self._eval_ttft
             )

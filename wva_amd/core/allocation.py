@@ -209,8 +209,12 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
     except AnalyzerError:
         return None
 
+    from ..analyzer import configured_ttft_tail
+
+    # WVA_TTFT_PERCENTILE: size to that percentile of TTFT, not to its mean
     target_perf = TargetPerf(
-        target_ttft=target.ttft, target_itl=target.itl, target_tps=target.tps
+        target_ttft=target.ttft, target_itl=target.itl, target_tps=target.tps,
+        ttft_tail=configured_ttft_tail(),
     )
     try:
         _, metrics, _ = qa.size(target_perf)

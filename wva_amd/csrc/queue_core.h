@@ -57,6 +57,28 @@ constexpr int kMaxQueueToBatchRatio = 10;    // K = (1 + ratio) * N
 //     (absent means 1.0 for every row, the Markovian model).
 // No vector, or a vector of all 1.0, gives results bit-identical to the
 // Markovian ones (x * 1.0 is exact, and fma(x, 1.0, y) rounds x + y).
+//
+// TTFT percentile (per-row waiting-time tail, "Waiting-time tail" below):
+//   - a sizing row may carry ttft_tail = eps, the allowed probability that
+//     TTFT exceeds target_ttft (p95 is eps = 0.05);
+//   - eps = 0 means "mean TTFT": the search compares the mean TTFT with the
+//     target, as it always did;
+//   - for eps > 0 the TTFT search runs on y(lam) = P(W > t(lam)) against the
+//     target value eps, with t(lam) = (target_ttft - prefill(eff_conc(lam)))
+//     / wait_scale and y = 1 when t <= 0 (the M/G/1 scaling stretches the
+//     waiting time by wait_scale, as it scales the mean); binary_search and
+//     classify_bracket are the same: eps below y(lam_min) is infeasible, eps
+//     above y(lam_max) gives lam_max;
+//   - the ITL search, the TPS back-off, the replica count and the final
+//     evaluation do not change, and R_TTFT stays the predicted MEAN TTFT at
+//     the final rate: only lam* moves, and through it the replica count;
+//   - eps must be finite with 0 <= eps < 1; any other value (NaN, +-inf,
+//     negative, >= 1) gives the all-zero result row in every implementation;
+//   - a row with target_ttft = 0 ignores a valid eps;
+//   - the layouts do not change: eps travels as a separate optional float64
+//     vector of length B, like scv (absent means 0 for every row).
+// No vector, or a vector of all 0, gives results bit-identical to the ones
+// without it on every path.
 enum ProblemField {
   P_ALPHA = 0,    // decode base (ms), >= 0
   P_BETA,         // decode slope (ms per batch unit), >= 0
@@ -91,6 +113,7 @@ struct Parms {
   int max_batch;   // N
   int num_decode;  // out_tokens-1, or 1 for decode-only single-token
   double wait_scale;  // (1 + scv) / 2; 1.0 is the Markovian model
+  double tail_eps;    // allowed P(TTFT > target); 0 sizes to the mean TTFT
 };
 
 // largest N whose chain length (1 + ratio) * N still fits an int
@@ -101,9 +124,11 @@ constexpr int kMaxBatchLimit = 2147483647 / (1 + kMaxQueueToBatchRatio);
 // than && or early returns): the kernels run this before anything else,
 // and nothing in it should make one load wait for another's compare.
 // scv is the row's service-time cs^2 (1.0 when the launch carries none):
-// finite and >= 0, so the -1 sentinel never passes.
-WVA_HD bool row_valid(const double *pr, double scv = 1.0) {
+// finite and >= 0, so the -1 sentinel never passes.  tail_eps is the row's
+// ttft_tail (0 when the launch carries none): 0 <= eps < 1.
+WVA_HD bool row_valid(const double *pr, double scv = 1.0, double tail_eps = 0.0) {
   bool ok = (scv >= 0.0) & (scv <= 1.7976931348623157e308);
+  ok &= (tail_eps >= 0.0) & (tail_eps < 1.0);
   for (int f = 0; f < PROBLEM_FIELDS; ++f) {
     ok &= fabs(pr[f]) <= 1.7976931348623157e308;  // fails NaN, +-inf
   }
@@ -117,7 +142,7 @@ WVA_HD bool row_valid(const double *pr, double scv = 1.0) {
 }
 
 // Model constants of a VALID row (the int casts are undefined otherwise).
-WVA_HD Parms parms_from_problem(const double *pr, double scv = 1.0) {
+WVA_HD Parms parms_from_problem(const double *pr, double scv = 1.0, double tail_eps = 0.0) {
   Parms p;
   p.alpha = pr[P_ALPHA];
   p.beta = pr[P_BETA];
@@ -129,6 +154,7 @@ WVA_HD Parms parms_from_problem(const double *pr, double scv = 1.0) {
   p.num_decode = p.out_tokens - 1;
   if (p.in_tokens == 0.0 && p.out_tokens == 1) p.num_decode = 1;
   p.wait_scale = (1.0 + scv) / 2.0;
+  p.tail_eps = tail_eps;
   return p;
 }
 
@@ -182,6 +208,11 @@ struct Stats {
   double wait;        // ms
   double serv;        // ms
   double n_serv;      // avg requests in service
+  // the normalisation, for the waiting-time tail alone: state n has
+  // probability exp(logp(n) - log_ref) / (accept_mass + e_K), and an accepted
+  // arrival sees it with probability exp(logp(n) - log_ref) / accept_mass
+  double accept_mass;  // S - e_K: the states 0..K-1, relative to e^log_ref
+  double log_ref;      // m, set by the evaluator that chose it
 };
 
 // Mode of the log-probability curve logp[n] = n*log(lam) - cum[n-1].
@@ -302,6 +333,8 @@ WVA_HD GeoTail geo_tail(double x_a, double d, int g_start, int n_hi, int K) {
 WVA_HD Stats stats_of_sums(double lam, int num, double S, double Ni, double Snum,
                            double Ninum, double eK) {
   Stats st;
+  st.accept_mass = S - eK;
+  st.log_ref = 0.0;
   st.throughput = lam * (1.0 - eK / S);
   double n_sys = Ni / S;
   st.n_serv = Ninum / S + (1.0 - Snum / S) * (double)num;
@@ -350,7 +383,9 @@ WVA_HD Stats eval_model(const Parms &p, const double *cum, int K, double lam) {
   S += tail.S;
   Ni += tail.Ni;
   eK += tail.eK;
-  return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+  Stats st = stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+  st.log_ref = m;
+  return st;
 }
 
 // ---------------------------------------------------------------------------
@@ -425,7 +460,9 @@ WVA_HD Stats eval_model_compact(const Parms &p, const double *cum, double log_mu
   S += tail.S;
   Ni += tail.Ni;
   eK += tail.eK;
-  return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+  Stats st = stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+  st.log_ref = m;
+  return st;
 }
 
 WVA_HD double eval_ttft_of(const Parms &p, const Stats &st) {
@@ -436,6 +473,116 @@ WVA_HD double eval_ttft_of(const Parms &p, const Stats &st) {
 WVA_HD double eval_itl_of(const Parms &p, const Stats &st) {
   double effc = effective_concurrency(p, st.serv);
   return decode_time(p, effc);
+}
+
+// ---------------------------------------------------------------------------
+// Waiting-time tail: P(W > t) of an accepted arrival, from the same chain.
+//
+// An accepted arrival sees state n with probability pi_n = p[n] / (1 - p[K])
+// (Poisson arrivals see time averages).  It waits only when n >= N, and then
+// for j = n - N + 1 departures at the constant full-batch rate mu_N =
+// serv_rate(N): W | n ~ Erlang(j, mu_N).  With x = mu_N * t and J = K - N,
+//
+//   P(W > t) = sum_{n=N..K-1} pi_n * sum_{i<j} e^-x x^i / i!.
+//
+// The states past N are geometric with ratio r = lam / mu_N, d = ln r < 0 on
+// the whole search bracket (lam_max = mu_N * (1 - kEpsilon)).  Swapping the
+// two sums leaves one sum of J terms,
+//
+//   P(W > t) = pi_N * sum_{i=0..J-1} T_i / expm1(d),
+//   T_i = exp(i * ln(x r) - x - lf[i]) * expm1((J - i) * d),   lf[i] = ln i!,
+//
+// i.e. Poisson(nu = x r = lam t) weights times g_i = (1 - r^(J-i)) / (1 - r),
+// which falls from at most J at i = 0 to 1 at i = J - 1.
+//
+// Window.  Only the terms within h of c = min(floor(nu), J - 1) are summed.
+// Against T_c (a term of the sum, so T_c <= sum), with L = ln(2e16) + 2 ln J:
+//   - left, i = c - s: the weights' ratio is prod_{k=i+1..c} k / nu <=
+//     prod_{q<s} (1 - q / c) <= exp(-s (s - 1) / (2 c)) because c <= nu, and
+//     g_i / g_c <= J; s > h >= sqrt(2 L c) makes every such term at most
+//     J e^-L T_c, and there are fewer than J of them: 0.5e-16 T_c in all;
+//   - right, i = c + s (only when c = floor(nu)): the ratio is
+//     prod_{k=c+1..i} nu / k <= prod_{q<s} 1 / (1 + q / (c + 1)) <=
+//     exp(-s (s - 1) / (2 (c + s))) (the Bernstein form of the Poisson upper
+//     tail), g_i <= g_c, and h = 2 L + 1 + sqrt(2 L c) gives s (s - 1) >=
+//     2 L (c + s) for every s > h: at most J e^-L T_c in all.
+// So what the window drops stays below 1e-16 of the sum.  Near saturation at
+// N = 700 it keeps about 2000 of the 7000 terms, elsewhere far fewer.
+// ---------------------------------------------------------------------------
+
+// The uniform scalars of one tail sum: every thread that shares an
+// evaluation computes the same ones.
+struct TailSweep {
+  bool certain;  // t <= 0: P(W > t) = 1, nothing to sum
+  double a;      // ln(x r)
+  double log_c;  // ln(pi_N) - x
+  double d;      // ln r
+  int J;         // terms of the whole sum
+  int lo, hi;    // the window: terms lo..hi
+};
+
+// st is the mean-model evaluation at lam and logp_n its log_p(N) (every table
+// holds cum[N-1]); t follows the contract above.
+WVA_HD TailSweep tail_sweep_of(const Parms &p, const Stats &st, double logp_n, double lam,
+                               double target_ttft) {
+  TailSweep w{true, 0.0, 0.0, 0.0, 0, 0, -1};
+  const double t =
+      (target_ttft - prefill_time(p, effective_concurrency(p, st.serv))) / p.wait_scale;
+  if (!(t > 0.0)) return w;
+  w.certain = false;
+  const double mu_n = serv_rate(p, p.max_batch);
+  const double x = mu_n * t;
+  w.d = log(lam) - log(mu_n);
+  w.a = log(x) + w.d;
+  w.log_c = logp_n - st.log_ref - log(st.accept_mass) - x;
+  w.J = p.max_batch * kMaxQueueToBatchRatio;
+  const double top = (double)(w.J - 1);
+  const double c = floor(fmin(lam * t, top));  // nu = x r = lam t
+  const double L = 37.54 + 2.0 * log((double)w.J);
+  const double h = 2.0 * L + 1.0 + sqrt(2.0 * L * c);
+  w.lo = (int)fmax(c - h, 0.0);
+  w.hi = (int)fmin(c + h, top);
+  return w;
+}
+
+// The tail sum given a log-factorial accessor lf(i) = ln i!: the window's
+// terms lo + first, lo + first + stride, ... (first = 0, stride = 1 is the
+// whole window; a workgroup's threads take first = tid, stride = THREADS and
+// add their results).  Two independent exp / expm1 chains per pass, as in the
+// mean model's sweep.  Every expm1 factor is negative: the result is <= 0.
+template <typename LogFact>
+WVA_HD double tail_sum(const TailSweep &w, const LogFact &lf, int first, int stride) {
+  double s0 = 0.0, s1 = 0.0;
+  int i = w.lo + first;
+  for (; i + stride <= w.hi; i += 2 * stride) {
+    const int i2 = i + stride;
+    const double e = exp((double)i * w.a - lf(i) + w.log_c);
+    const double e2 = exp((double)i2 * w.a - lf(i2) + w.log_c);
+    s0 += e * expm1((double)(w.J - i) * w.d);
+    s1 += e2 * expm1((double)(w.J - i2) * w.d);
+  }
+  if (i <= w.hi) {
+    s0 += exp((double)i * w.a - lf(i) + w.log_c) * expm1((double)(w.J - i) * w.d);
+  }
+  return s0 + s1;
+}
+
+// P(W > t) from the reduced tail sum; the clamp only trims rounding
+WVA_HD double tail_probability(const TailSweep &w, double sum) {
+  return fmin(fmax(sum / expm1(w.d), 0.0), 1.0);
+}
+
+// Whether an evaluator offers exceedance(lam, target_ttft) = P(TTFT > target)
+// next to eval(lam); one that does not sizes to the mean TTFT alone, and the
+// callers route no row with ttft_tail > 0 to it.
+template <typename Ev>
+constexpr auto has_exceedance(int) -> decltype((void)((const Ev *)nullptr)->exceedance(0.0, 0.0),
+                                               true) {
+  return true;
+}
+template <typename Ev>
+constexpr bool has_exceedance(long) {
+  return false;
 }
 
 // ---------------------------------------------------------------------------
@@ -532,8 +679,20 @@ WVA_HD bool search_targets(const double *pr, const Parms &p, const Ev &ev, doubl
                            double lam_max, double *lam_ttft, double *lam_itl) {
   *lam_ttft = lam_max;
   if (pr[P_TARGET_TTFT] > 0.0) {
-    auto ttft = [&](double lam) { return eval_ttft_of(p, ev.eval(lam)); };
-    if (binary_search(lam_min, lam_max, pr[P_TARGET_TTFT], ttft, lam_ttft) < 0) return false;
+    // the TTFT functional: the tail P(TTFT > target) against eps for a row
+    // that carries one, the mean TTFT against the target otherwise
+    bool to_percentile = false;
+    if constexpr (has_exceedance<Ev>(0)) {
+      if (p.tail_eps > 0.0) {
+        to_percentile = true;
+        auto tail = [&](double lam) { return ev.exceedance(lam, pr[P_TARGET_TTFT]); };
+        if (binary_search(lam_min, lam_max, p.tail_eps, tail, lam_ttft) < 0) return false;
+      }
+    }
+    if (!to_percentile) {
+      auto ttft = [&](double lam) { return eval_ttft_of(p, ev.eval(lam)); };
+      if (binary_search(lam_min, lam_max, pr[P_TARGET_TTFT], ttft, lam_ttft) < 0) return false;
+    }
   }
   *lam_itl = lam_max;
   if (pr[P_TARGET_ITL] > 0.0) {

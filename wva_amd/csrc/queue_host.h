@@ -28,10 +28,37 @@ inline void fill_cum(const Parms &p, int len, double *cum) {
   }
 }
 
+// lf[i] = ln i! for i in [0, len): the waiting-time tail's table.  It does
+// not depend on the row, so a batch fills one, as long as its longest tail
+// sum, and every row reads it.
+inline std::vector<double> log_factorials(long long len) {
+  std::vector<double> lf((size_t)(len > 0 ? len : 0));
+  double acc = 0.0;
+  for (long long i = 0; i < len; ++i) {
+    if (i > 0) acc += log((double)i);
+    lf[(size_t)i] = acc;
+  }
+  return lf;
+}
+
+// P(TTFT > target_ttft) at lam over either table policy below (queue_core.h,
+// "Waiting-time tail"): the mean-model evaluation, then the windowed tail sum
+// over lf.  cum_last = cum[N-1], which both tables hold.
+template <typename Table>
+inline double host_exceedance(const Table &table, const double *lf, double cum_last,
+                              double lam, double target_ttft) {
+  const Parms &p = table.p;
+  const double logp_n = (double)p.max_batch * log(lam) - cum_last;
+  const TailSweep w = tail_sweep_of(p, table.eval(lam), logp_n, lam, target_ttft);
+  if (w.certain) return 1.0;
+  return tail_probability(w, tail_sum(w, [lf](int i) { return lf[i]; }, 0, 1));
+}
+
 // Table policies of solve_one: how long a row's table is, how it is filled,
 // and which eval_model* reads it.  Each is an evaluator for solve_row.  The
 // constructor WRITES the caller's scratch table (the log_mu scan) and the
-// object then only reads it.
+// object then only reads it.  lf is log_factorials over at least 10 * N
+// entries for a row with ttft_tail > 0, and is not read otherwise.
 
 // K = 11 * N doubles, evaluated inside the significance window (state_window)
 struct HostFullTable {
@@ -39,11 +66,15 @@ struct HostFullTable {
   const Parms &p;
   const double *cum;
   int K;
-  HostFullTable(const Parms &parms, double *table)
-      : p(parms), cum(table), K(parms.max_batch * (1 + kMaxQueueToBatchRatio)) {
+  const double *lf;
+  HostFullTable(const Parms &parms, double *table, const double *log_fact = nullptr)
+      : p(parms), cum(table), K(parms.max_batch * (1 + kMaxQueueToBatchRatio)), lf(log_fact) {
     fill_cum(p, K, table);
   }
   Stats eval(double lam) const { return eval_model(p, cum, K, lam); }
+  double exceedance(double lam, double target_ttft) const {
+    return host_exceedance(*this, lf, cum[p.max_batch - 1], lam, target_ttft);
+  }
 };
 
 // N doubles (queue_core.h, "Compact table"); no window
@@ -52,23 +83,30 @@ struct HostCompactTable {
   const Parms &p;
   const double *cum;
   double log_mu_n;
-  HostCompactTable(const Parms &parms, double *table)
-      : p(parms), cum(table), log_mu_n(log_mu(parms, parms.max_batch - 1)) {
+  const double *lf;
+  HostCompactTable(const Parms &parms, double *table, const double *log_fact = nullptr)
+      : p(parms), cum(table), log_mu_n(log_mu(parms, parms.max_batch - 1)), lf(log_fact) {
     fill_cum(p, p.max_batch, table);
   }
   Stats eval(double lam) const { return eval_model_compact(p, cum, log_mu_n, lam); }
+  double exceedance(double lam, double target_ttft) const {
+    return host_exceedance(*this, lf, cum[p.max_batch - 1], lam, target_ttft);
+  }
 };
 
 // Scalar solve of one problem (CPU path).  cum must hold Table::length(pr)
 // doubles; a row that breaks the contract of queue_core.h yields the
 // all-zero row and touches no table.  scv is the row's service-time cs^2
 // (1.0: Markovian); it only enters through Parms::wait_scale in eval_ttft_of.
+// tail_eps is the row's ttft_tail (0: size to the mean TTFT) and lf the
+// batch's log_factorials, at least batch_tail_length long.
 template <typename Table>
-inline void solve_one(const double *pr, double *out, double *cum, double scv = 1.0) {
+inline void solve_one(const double *pr, double *out, double *cum, double scv = 1.0,
+                      double tail_eps = 0.0, const double *lf = nullptr) {
   for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
-  if (!row_valid(pr, scv)) return;
-  const Parms p = parms_from_problem(pr, scv);
-  const Table table(p, cum);  // fills cum: the O(table length) build happens here
+  if (!row_valid(pr, scv, tail_eps)) return;
+  const Parms p = parms_from_problem(pr, scv, tail_eps);
+  const Table table(p, cum, lf);  // fills cum: the O(table length) build happens here
   const RowValues vals = solve_row(pr, p, table);
   out[R_FEASIBLE] = vals.feasible;
   out[R_REPLICAS] = vals.replicas;
@@ -84,6 +122,20 @@ inline int batch_table_length(const double *pr, long long rows) {
   int longest = 1;
   for (long long i = 0; i < rows; ++i) {
     const int len = Table::length(pr + i * PROBLEM_FIELDS);  // 0 if invalid
+    if (len > longest) longest = len;
+  }
+  return longest;
+}
+
+// Length of the log-factorial table a batch needs: 10 * N of its largest
+// valid row that carries a ttft_tail, 0 without a vector.
+inline long long batch_tail_length(const double *pr, const double *tail, long long rows) {
+  long long longest = 0;
+  if (tail == nullptr) return longest;
+  for (long long i = 0; i < rows; ++i) {
+    const double *row = pr + i * PROBLEM_FIELDS;
+    if (!(tail[i] > 0.0) || !row_valid(row)) continue;
+    const long long len = (long long)row[P_MAX_BATCH] * kMaxQueueToBatchRatio;
     if (len > longest) longest = len;
   }
   return longest;

@@ -48,44 +48,56 @@ static void check_problems(const torch::Tensor &problems) {
 // scv: optional per-row service-time cs^2 (queue_core.h, M/G/1 correction):
 // float64, contiguous, [B], on the device of problems.  Absent is the
 // Markovian model, bit-identical to a vector of ones, and gives nullptr.
+// ttft_tail (queue_core.h, TTFT percentile) travels the same way; absent is
+// 0 for every row, the mean TTFT.
 static const double *scv_data(const c10::optional<torch::Tensor> &scv,
-                              const torch::Tensor &problems) {
+                              const torch::Tensor &problems, const char *name = "scv") {
   if (!scv.has_value()) return nullptr;
   const torch::Tensor &v = *scv;
   const int64_t B = problems.size(0);
-  TORCH_CHECK(v.scalar_type() == torch::kFloat64, "scv must be float64");
-  TORCH_CHECK(v.dim() == 1 && v.size(0) == B, "scv must be [B] = [", B, "]");
-  TORCH_CHECK(v.is_contiguous(), "scv must be contiguous");
-  TORCH_CHECK(v.device() == problems.device(), "scv must be on the device of problems");
+  TORCH_CHECK(v.scalar_type() == torch::kFloat64, name, " must be float64");
+  TORCH_CHECK(v.dim() == 1 && v.size(0) == B, name, " must be [B] = [", B, "]");
+  TORCH_CHECK(v.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(v.device() == problems.device(), name, " must be on the device of problems");
   return B > 0 ? v.data_ptr<double>() : nullptr;
 }
 
 // The host solve of a contiguous CPU batch over either table policy of
 // queue_host.h; scratch is sized by the longest table in the batch.
 template <typename Table>
-static torch::Tensor solve_on_cpu(const torch::Tensor &problems, const double *scv_ptr) {
+static torch::Tensor solve_on_cpu(const torch::Tensor &problems, const double *scv_ptr,
+                                  const double *tail_ptr) {
   const int64_t B = problems.size(0);
   auto out = torch::zeros({B, (int64_t)wva::RESULT_FIELDS}, problems.options());
   if (B == 0) return out;
   const double *pr = problems.data_ptr<double>();
   double *res = out.data_ptr<double>();
   const int table_len = wva::batch_table_length<Table>(pr, B);
+  const std::vector<double> lf = wva::log_factorials(wva::batch_tail_length(pr, tail_ptr, B));
   at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
     std::vector<double> cum((size_t)table_len);
     for (int64_t i = begin; i < end; ++i) {
       wva::solve_one<Table>(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
-                            cum.data(), scv_ptr ? scv_ptr[i] : 1.0);
+                            cum.data(), scv_ptr ? scv_ptr[i] : 1.0,
+                            tail_ptr ? tail_ptr[i] : 0.0, lf.data());
     }
   });
   return out;
 }
 
 static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hint = -1,
-                                       c10::optional<torch::Tensor> scv = c10::nullopt) {
+                                       c10::optional<torch::Tensor> scv = c10::nullopt,
+                                       c10::optional<torch::Tensor> ttft_tail = c10::nullopt) {
   check_problems(problems);
   problems = problems.contiguous();
   const double *scv_ptr = scv_data(scv, problems);
-  if (!problems.is_cuda()) return solve_on_cpu<wva::HostFullTable>(problems, scv_ptr);
+  const double *tail_ptr = scv_data(ttft_tail, problems, "ttft_tail");
+  if (!problems.is_cuda()) {
+    return solve_on_cpu<wva::HostFullTable>(problems, scv_ptr, tail_ptr);
+  }
+  // the full-table kernels size to the mean TTFT alone
+  TORCH_CHECK(!ttft_tail.has_value(),
+              "ttft_tail on the GPU goes through submit_tail, not solve_allocations");
 
   // the GPU kernels write all six fields of every row (rejected rows
   // included), so the output needs no zeroing
@@ -133,11 +145,13 @@ static torch::Tensor solve_allocations(torch::Tensor problems, int64_t max_k_hin
 // instead of 11 * N.  CPU tensors only; on the GPU the compact kernel is
 // reached through submit_compact.
 static torch::Tensor solve_allocations_compact(
-    torch::Tensor problems, c10::optional<torch::Tensor> scv = c10::nullopt) {
+    torch::Tensor problems, c10::optional<torch::Tensor> scv = c10::nullopt,
+    c10::optional<torch::Tensor> ttft_tail = c10::nullopt) {
   check_problems(problems);
   TORCH_CHECK(!problems.is_cuda(), "solve_allocations_compact takes CPU tensors");
   problems = problems.contiguous();
-  return solve_on_cpu<wva::HostCompactTable>(problems, scv_data(scv, problems));
+  return solve_on_cpu<wva::HostCompactTable>(problems, scv_data(scv, problems),
+                                             scv_data(ttft_tail, problems, "ttft_tail"));
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -145,10 +159,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("solve_allocations", &solve_allocations,
         "Batched state-dependent M/M/1/K allocation sizing",
         pybind11::arg("problems"), pybind11::arg("max_k_hint") = -1,
-        pybind11::arg("scv") = pybind11::none());
+        pybind11::arg("scv") = pybind11::none(), pybind11::arg("ttft_tail") = pybind11::none());
   m.def("solve_allocations_compact", &solve_allocations_compact,
         "The same sizing on the CPU over the compact table (N doubles per row)",
-        pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none());
+        pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
+        pybind11::arg("ttft_tail") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
   // greedy_solve, HAS_GREEDY
@@ -166,6 +181,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batch N the launch reserves LDS for (N doubles, up to ~7800); same "
         "slot pool, stream, checks and collect as submit",
         pybind11::arg("problems"), pybind11::arg("max_n"),
+        pybind11::arg("scv") = pybind11::none());
+  m.def("submit_tail", &wva::dispatch::submit_tail,
+        "submit through the waiting-time tail kernel: rows sized to a TTFT "
+        "percentile, tail the float64 [B] vector of their ttft_tail; max_n is "
+        "the largest max batch N the launch reserves LDS for (11 * N doubles, "
+        "up to 700); same slot pool, stream, checks and collect as submit",
+        pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("tail"),
         pybind11::arg("scv") = pybind11::none());
   m.def("collect", &wva::dispatch::collect,
         "Wait (GIL released) for a ticket and return its float64 [B, 6] results",

@@ -19,16 +19,17 @@ namespace py = pybind11;
 
 // One body for both table policies of queue_host.h: the full table
 // (solve_allocations) and the compact one, N doubles of scratch per row
-// instead of 11 * N (solve_allocations_compact).  scv: scv_arg.h.
+// instead of 11 * N (solve_allocations_compact).  scv, ttft_tail: scv_arg.h.
 template <typename Table>
 static py::array_t<double> solve_allocations(
     py::array_t<double, py::array::c_style | py::array::forcecast> problems,
-    py::object scv) {
+    py::object scv, py::object ttft_tail) {
   auto buf = problems.request();
   if (buf.ndim != 2 || buf.shape[1] != (ssize_t)wva::PROBLEM_FIELDS)
     throw std::invalid_argument("problems must be [B, 12] float64");
   const ssize_t B = buf.shape[0];
   const double *scv_ptr = wva::scv_data(scv, B);
+  const double *tail_ptr = wva::row_vector_data(ttft_tail, B, "ttft_tail");
   auto out = py::array_t<double>({B, (ssize_t)wva::RESULT_FIELDS});
   auto out_buf = out.request();
   const double *pr = (const double *)buf.ptr;
@@ -37,6 +38,8 @@ static py::array_t<double> solve_allocations(
   if (B == 0) return out;
 
   const int table_len = wva::batch_table_length<Table>(pr, B);
+  const std::vector<double> lf =
+      wva::log_factorials(wva::batch_tail_length(pr, tail_ptr, B));
   {
     py::gil_scoped_release release;
 #pragma omp parallel
@@ -45,7 +48,8 @@ static py::array_t<double> solve_allocations(
 #pragma omp for schedule(dynamic, 8)
       for (ssize_t i = 0; i < B; ++i) {
         wva::solve_one<Table>(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
-                              cum.data(), scv_ptr ? scv_ptr[i] : 1.0);
+                              cum.data(), scv_ptr ? scv_ptr[i] : 1.0,
+                              tail_ptr ? tail_ptr[i] : 0.0, lf.data());
       }
     }
   }
@@ -56,10 +60,11 @@ PYBIND11_MODULE(_queue_native_cpu, m) {
   m.doc() = "wva_amd torch-free batched queue solver (CPU/OpenMP)";
   m.def("solve_allocations", &solve_allocations<wva::HostFullTable>,
         "Batched state-dependent M/M/1/K allocation sizing", py::arg("problems"),
-        py::arg("scv") = py::none());
+        py::arg("scv") = py::none(), py::arg("ttft_tail") = py::none());
   m.def("solve_allocations_compact", &solve_allocations<wva::HostCompactTable>,
         "The same sizing over the compact table (N doubles per row)",
-        py::arg("problems"), py::arg("scv") = py::none());
+        py::arg("problems"), py::arg("scv") = py::none(),
+        py::arg("ttft_tail") = py::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
   // limited-mode greedy solve (greedy_core.h): greedy_solve, HAS_GREEDY

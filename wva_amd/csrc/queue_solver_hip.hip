@@ -61,7 +61,9 @@ namespace wva {
 //   - 896 (depth-3 speculation; measured slower than depth 2).
 // The launcher auto-selects (occupancy-aware, see wva_launch_solve_scv);
 // WVA_GPU_THREADS=64|128|256|384|896 overrides, read per launch.  A sixth
-// kernel runs the 256 body over the compact table (N doubles, not 11*N).
+// kernel runs the 256 body over the compact table (N doubles, not 11*N), and
+// a seventh sizes rows to a TTFT percentile (the waiting-time tail kernel at
+// the end of the namespace: compact table plus a log-factorial table).
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -294,7 +296,9 @@ struct WgEval {
     S += tail.S;
     Ni += tail.Ni;
     eK += tail.eK;
-    return stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+    Stats st = stats_of_sums(lam, num, S, Ni, Snum, Ninum, eK);
+    st.log_ref = m;  // read by the tail kernel alone
+    return st;
   }
 };
 
@@ -312,8 +316,9 @@ __device__ inline double row_scv(const double *scv, int pid) {
 // row, so the early return it decides is uniform and precedes the first
 // barrier.
 template <typename Table>
-__device__ inline bool row_rejected(const double *pr, double scv, int reserved) {
-  return !(row_valid(pr, scv) & Table::fits(pr, reserved));
+__device__ inline bool row_rejected(const double *pr, double scv, int reserved,
+                                    double tail_eps = 0.0) {
+  return !(row_valid(pr, scv, tail_eps) & Table::fits(pr, reserved));
 }
 
 // Result stores.  Threads 0..RESULT_FIELDS-1 zero the row once, first thing
@@ -337,24 +342,31 @@ __device__ inline void store_row(double *res, const RowValues vals) {
   }
 }
 
-// chunked parallel inclusive scan of log_mu over K states into LDS
-template <int THREADS>
-__device__ void build_cum(const Parms &p, int K, double *cum, double *totals) {
+// chunked parallel inclusive scan of term(n), n in [0, len), into LDS; ends
+// with a barrier, so totals may be reused by the next scan
+template <int THREADS, typename Term>
+__device__ void scan_table(int len, double *table, double *totals, Term term) {
   const int tid = threadIdx.x;
-  const int chunk = (K + THREADS - 1) / THREADS;
+  const int chunk = (len + THREADS - 1) / THREADS;
   const int lo = tid * chunk;
-  const int hi = min(lo + chunk, K);
+  const int hi = min(lo + chunk, len);
   double acc = 0.0;
   for (int n = lo; n < hi; ++n) {
-    acc += log_mu(p, n);
-    cum[n] = acc;
+    acc += term(n);
+    table[n] = acc;
   }
-  totals[tid] = (lo < K) ? acc : 0.0;
+  totals[tid] = (lo < len) ? acc : 0.0;
   __syncthreads();
   double offset = 0.0;
   for (int t = 0; t < tid; ++t) offset += totals[t];  // broadcast LDS reads
-  for (int n = lo; n < hi; ++n) cum[n] += offset;
+  for (int n = lo; n < hi; ++n) table[n] += offset;
   __syncthreads();
+}
+
+// the cumulative table: the scan of log_mu over K states
+template <int THREADS>
+__device__ void build_cum(const Parms &p, int K, double *cum, double *totals) {
+  scan_table<THREADS>(K, cum, totals, [&](int n) { return log_mu(p, n); });
 }
 
 // Sequential body: the whole workgroup evaluates one rate at a time and runs
@@ -363,30 +375,49 @@ __device__ void build_cum(const Parms &p, int K, double *cum, double *totals) {
 // infeasibility exit and the evaluator's barriers are reached uniformly.
 // `reserved` is the table length the launch reserved LDS for (max_k for the
 // full table, max_n for the compact one).
-// LDS: cum[reserved], totals[THREADS], red[WAVES * 5] of the 64 slack doubles.
-template <int THREADS, typename Table>
+// LDS: cum[reserved], whatever the row policy keeps behind it, totals[THREADS],
+// red[WAVES * 5] of the 64 slack doubles.
+//
+// Rows is the row policy: what a row carries besides its cs^2, how many
+// doubles of tables the launch reserved, and the evaluator that solve_row
+// runs over.  MeanRows is every mean-TTFT kernel: no ttft_tail, the table
+// alone, WgEval.  TailRows (the waiting-time tail kernel below) adds the
+// row's eps, the log-factorial table and the tail sum.
+struct MeanRows {
+  static __device__ double eps(const double *, int) { return 0.0; }
+  static __device__ int table_doubles(int reserved) { return reserved; }
+  template <int THREADS, typename Table>
+  static __device__ WgEval<THREADS, Table> evaluator(const Parms &p, const Table &table,
+                                                     double *, double *, double *red) {
+    return {p, table, red};
+  }
+};
+
+template <int THREADS, typename Table, typename Rows = MeanRows>
 __device__ void solve_body(const double *__restrict__ prob,
                            const double *__restrict__ scv, double *__restrict__ out,
-                           int n_problems, int reserved) {
+                           int n_problems, int reserved,
+                           const double *__restrict__ tail = nullptr) {
   const int pid = blockIdx.x;
   if (pid >= n_problems) return;
   const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
   double *res = out + (size_t)pid * RESULT_FIELDS;
 
   const double cs2 = row_scv(scv, pid);
+  const double eps = Rows::eps(tail, pid);
   zero_row(res);
-  if (row_rejected<Table>(pr, cs2, reserved)) return;
-  const Parms p = parms_from_problem(pr, cs2);
+  if (row_rejected<Table>(pr, cs2, reserved, eps)) return;
+  const Parms p = parms_from_problem(pr, cs2, eps);
 
   extern __shared__ double smem[];
-  double *cum = smem;                // this problem's table
-  double *totals = smem + reserved;  // THREADS chunk totals
+  double *cum = smem;                                     // this problem's table
+  double *totals = smem + Rows::table_doubles(reserved);  // THREADS chunk totals
   double *red = totals + THREADS;
 
   const Table table(p, cum);
   build_cum<THREADS>(p, table.scan_length(), cum, totals);
 
-  WgEval<THREADS, Table> ev{p, table, red};
+  const auto ev = Rows::template evaluator<THREADS>(p, table, cum + reserved, totals, red);
   store_row(res, solve_row(pr, p, ev));
 }
 
@@ -664,7 +695,7 @@ __device__ int spec_binary_search(double x_min, double x_max, double y_target,
 //   [14..20] group-1 y slots      [21..27] group-1 flags
 //   [28..31] results: lam0, ind0, lam1, ind1
 //   [32..33] done flags per group
-//   [40..47] depth 3 only: the row's Parms (see below)
+//   [40..48] depth 3 only: the row's Parms (see below)
 template <int D>
 __device__ void solve_body_spec(const double *__restrict__ prob,
                                 const double *__restrict__ scv,
@@ -693,11 +724,11 @@ __device__ void solve_body_spec(const double *__restrict__ prob,
   double *mail = totals + THREADS;
   if (tid < 34) mail[tid] = 0.0;
   // The 896-thread geometry has 128 vector registers per lane and spills:
-  // there the searches read the row's constants from LDS (8 of the 64
+  // there the searches read the row's constants from LDS (9 of the 64
   // slack doubles, published by the scan's closing barrier) instead of
   // holding all of them, wait_scale included, in registers.  Same values,
   // same arithmetic.
-  static_assert(sizeof(Parms) <= 8 * sizeof(double), "Parms outgrew its LDS slot");
+  static_assert(sizeof(Parms) <= 9 * sizeof(double), "Parms outgrew its LDS slot");
   const Parms *pp = &p0;
   if constexpr (D == 3) {
     Parms *shared_parms = reinterpret_cast<Parms *>(mail + 40);
@@ -790,6 +821,88 @@ extern "C" __global__ void __launch_bounds__(kCompactThreads) wva_solve_kernel_c
   solve_body<kCompactThreads, LdsCompactTable>(prob, scv, out, n_problems, max_n);
 }
 
+// ---------------------------------------------------------------------------
+// Waiting-time tail kernel: rows sized to a TTFT percentile (queue_core.h,
+// "TTFT percentile" and "Waiting-time tail").  One workgroup of 256 threads
+// per row, workgroup barriers only.
+//
+// LDS (doubles): cum[max_n], the compact cumulative table; lf[10 * max_n],
+// lf[i] = ln i!; totals[256]; red[20] of the mean-model evaluator and
+// tail_red[4] behind it, of the 64 slack doubles.  That is 11 * max_n + 256
+// + 64, the footprint of the full table, so N stays <= ~700.  Both tables
+// come out of the same chunked scan (lf is the scan of ln i), two barriers
+// each.
+//
+// One evaluation of y(lam) = P(TTFT > target):
+//   - the mean-model sums, exactly WgEval<256, LdsCompactTable>::eval (its
+//     two barriers): they give t(lam) through the effective concurrency, and
+//     pi_N through the normalisation (Stats::accept_mass, Stats::log_ref);
+//   - tail_sweep_of (queue_core.h): the closed-form window of at most
+//     2 h + 1 terms around min(floor(lam t), J - 1), uniform over the
+//     workgroup, so no thread searches for anything;
+//   - the tail sum over that window: thread tid takes terms lo + tid, lo +
+//     tid + 256, ... (tail_sum: two exp / expm1 chains per pass; consecutive
+//     lanes read consecutive lf entries, conflict-free), then the same
+//     __shfl_down reduction and one more barrier for the cross-wave combine.
+// tail_red is apart from red, so that third barrier is the only one the tail
+// adds: a thread may still be reading red's totals when another already
+// writes its wave's tail partial, and the next evaluation's first barrier
+// comes before anything writes tail_red again.  Every thread gets the same y
+// (broadcast LDS reads), so binary_search runs in lockstep as in solve_body
+// and every barrier is reached by all 256 threads.
+// ---------------------------------------------------------------------------
+constexpr int kTailThreads = 256;
+
+struct WgTailEval {
+  static constexpr int WAVES = kTailThreads / 64;
+  const Parms &p;
+  WgEval<kTailThreads, LdsCompactTable> mean;
+  const double *lf;  // LDS, 10 * N entries
+  double *tail_red;  // LDS, WAVES
+
+  __device__ Stats eval(double lam) const { return mean.eval(lam); }
+
+  __device__ double exceedance(double lam, double target_ttft) const {
+    const Stats st = mean.eval(lam);
+    const double logp_n = mean.table.log_p(log(lam), p.max_batch);
+    const TailSweep w = tail_sweep_of(p, st, logp_n, lam, target_ttft);
+    if (w.certain) return 1.0;  // uniform: st is the same on every thread
+    const double *table = lf;
+    double sum = tail_sum(w, [table](int i) { return table[i]; }, (int)threadIdx.x,
+                          kTailThreads);
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) tail_red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    sum = 0.0;
+    for (int wv = 0; wv < WAVES; ++wv) sum += tail_red[wv];
+    return tail_probability(w, sum);
+  }
+};
+
+// solve_body's row policy of the tail kernel: the row's eps from the launch's
+// vector, cum[max_n] and lf[10 * max_n] reserved, and an evaluator that first
+// scans lf (behind cum, after build_cum's closing barrier freed totals).
+struct TailRows {
+  static __device__ double eps(const double *tail, int pid) { return tail[pid]; }
+  static __device__ int table_doubles(int max_n) {
+    return max_n * (1 + kMaxQueueToBatchRatio);
+  }
+  template <int THREADS, typename Table>
+  static __device__ WgTailEval evaluator(const Parms &p, const Table &table, double *lf,
+                                         double *totals, double *red) {
+    static_assert(THREADS == kTailThreads, "the tail evaluator is a 256-thread one");
+    scan_table<THREADS>(p.max_batch * kMaxQueueToBatchRatio, lf, totals,
+                        [](int i) { return i == 0 ? 0.0 : log((double)i); });
+    return {p, {p, table, red}, lf, red + 5 * WgTailEval::WAVES};
+  }
+};
+
+extern "C" __global__ void __launch_bounds__(kTailThreads) wva_solve_kernel_tail(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    const double *__restrict__ tail, double *__restrict__ out, int n_problems, int max_n) {
+  solve_body<kTailThreads, LdsCompactTable, TailRows>(prob, scv, out, n_problems, max_n, tail);
+}
+
 }  // namespace wva
 
 #include <cstdlib>
@@ -875,4 +988,21 @@ extern "C" int wva_launch_solve_compact(const double *prob, const double *scv, d
                                         int n_problems, int max_n, void *stream) {
   const Geometry compact{wva::kCompactThreads, "", wva::wva_solve_kernel_compact};
   return launch(compact, prob, scv, out, n_problems, max_n, stream);
+}
+
+// Waiting-time tail launch: tail is the device vector of the rows' ttft_tail
+// (n_problems doubles, required), max_n the largest trunc(N) the launch
+// reserves LDS for: cum[max_n] and lf[10 * max_n].  Return values as launch()
+// above: -1, and nothing launched, without a tail vector or when the tables
+// do not fit 64 KiB (max_n beyond ~715).
+extern "C" int wva_launch_solve_tail(const double *prob, const double *scv, const double *tail,
+                                     double *out, int n_problems, int max_n, void *stream) {
+  constexpr int kPerState = 1 + wva::kMaxQueueToBatchRatio;
+  if (tail == nullptr || max_n < 1 || max_n > 64 * 1024 / 8 / kPerState) return -1;
+  const int table_len = max_n * kPerState;
+  if (!fits_lds(table_len, wva::kTailThreads)) return -1;
+  const size_t smem = (size_t)(table_len + wva::kTailThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_solve_kernel_tail, dim3(n_problems), dim3(wva::kTailThreads), smem,
+                     (hipStream_t)stream, prob, scv, tail, out, n_problems, max_n);
+  return (int)hipGetLastError();
 }

@@ -22,7 +22,8 @@
 // the B rows, so the one upload copy moves both and nothing is created per
 // call.  A submit without one uploads the rows alone and launches with a
 // null vector: whatever an earlier submit left behind the rows of a reused
-// slot is never read.
+// slot is never read.  A submit_tail carries one more vector, the rows'
+// ttft_tail, behind that, in the same upload.
 //
 // Buffers live in a pool of slots, each with pinned in/out, device in/out
 // and an event created with hipEventDisableTiming.  Slots are grow-only;
@@ -60,6 +61,8 @@ extern "C" int wva_launch_solve_scv(const double *prob, const double *scv, doubl
                                     int n_problems, int max_k, void *stream);
 extern "C" int wva_launch_solve_compact(const double *prob, const double *scv, double *out,
                                         int n_problems, int max_n, void *stream);
+extern "C" int wva_launch_solve_tail(const double *prob, const double *scv, const double *tail,
+                                     double *out, int n_problems, int max_n, void *stream);
 
 namespace wva {
 namespace dispatch {
@@ -92,7 +95,7 @@ struct DeviceGuard {
 enum class SlotState { kFree, kInFlight, kCollecting };
 
 struct Slot {
-  double *h_in = nullptr;   // pinned, cap_rows * (PROBLEM_FIELDS + 1): rows, then scv
+  double *h_in = nullptr;   // pinned, cap_rows * (PROBLEM_FIELDS + 2): rows, scv, tail
   double *h_out = nullptr;  // pinned, cap_rows * RESULT_FIELDS
   double *d_in = nullptr;
   double *d_out = nullptr;
@@ -129,8 +132,9 @@ inline void grow_slot(Slot &s, int64_t rows) {
   s.h_in = s.h_out = s.d_in = s.d_out = nullptr;
   s.cap_rows = 0;
   const int64_t cap = (rows + 255) / 256 * 256;
-  // one more double per row: the optional cs^2 vector behind the rows
-  const size_t in_bytes = (size_t)cap * (PROBLEM_FIELDS + 1) * sizeof(double);
+  // two more doubles per row: the optional cs^2 and ttft_tail vectors
+  // behind the rows
+  const size_t in_bytes = (size_t)cap * (PROBLEM_FIELDS + 2) * sizeof(double);
   const size_t out_bytes = (size_t)cap * RESULT_FIELDS * sizeof(double);
   hip_check(hipHostMalloc((void **)&s.h_in, in_bytes, hipHostMallocDefault),
             "hipHostMalloc");
@@ -141,16 +145,17 @@ inline void grow_slot(Slot &s, int64_t rows) {
   s.cap_rows = cap;
 }
 
-// either launcher of queue_solver_hip.hip
-using Launcher = int (*)(const double *prob, const double *scv, double *out, int n_problems,
-                         int table_len, void *stream);
+// any launcher of queue_solver_hip.hip; tail is null unless the submit
+// carries a ttft_tail vector, which only the tail kernel's launcher reads
+using Launcher = int (*)(const double *prob, const double *scv, const double *tail, double *out,
+                         int n_problems, int table_len, void *stream);
 
 // The one submit.  `launch` gets table_len clamped to an int; when it answers
 // -1 (nothing was launched) the error reads not_fit_head, table_len,
 // not_fit_tail.
 inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t table_len,
                            const py::object &scv, const char *not_fit_head,
-                           const char *not_fit_tail) {
+                           const char *not_fit_tail, const py::object &tail = py::none()) {
   if (!py::isinstance<py::array_t<double>>(problems)) {
     throw py::type_error("problems must be a float64 array");
   }
@@ -164,6 +169,7 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
   const int64_t B = problems.shape(0);
   if (B > INT_MAX) throw py::value_error("too many problems for one launch");
   const double *scv_src = scv_data(scv, B);
+  const double *tail_src = row_vector_data(tail, B, "tail");
 
   Pool &P = pool();
   std::lock_guard<std::mutex> lock(P.mu);
@@ -203,19 +209,25 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
   grow_slot(*slot, B);
 
   const size_t row_doubles = (size_t)B * PROBLEM_FIELDS;
-  const size_t in_doubles = row_doubles + (scv_src != nullptr ? (size_t)B : 0);
+  const size_t scv_doubles = scv_src != nullptr ? (size_t)B : 0;
+  const size_t in_doubles = row_doubles + scv_doubles + (tail_src != nullptr ? (size_t)B : 0);
   const size_t out_bytes = (size_t)B * RESULT_FIELDS * sizeof(double);
   std::memcpy(slot->h_in, problems.data(), row_doubles * sizeof(double));
   if (scv_src != nullptr) {
     std::memcpy(slot->h_in + row_doubles, scv_src, (size_t)B * sizeof(double));
+  }
+  if (tail_src != nullptr) {
+    std::memcpy(slot->h_in + row_doubles + scv_doubles, tail_src, (size_t)B * sizeof(double));
   }
   hip_check(hipMemcpyAsync(slot->d_in, slot->h_in, in_doubles * sizeof(double),
                            hipMemcpyHostToDevice, P.stream),
             "hipMemcpyAsync (upload)");
   const int len = table_len > INT_MAX ? INT_MAX : (table_len < 0 ? 0 : (int)table_len);
   const double *d_scv = scv_src != nullptr ? slot->d_in + row_doubles : nullptr;
+  const double *d_tail =
+      tail_src != nullptr ? slot->d_in + row_doubles + scv_doubles : nullptr;
   const int status =
-      launch(slot->d_in, d_scv, slot->d_out, (int)B, len, (void *)P.stream);
+      launch(slot->d_in, d_scv, d_tail, slot->d_out, (int)B, len, (void *)P.stream);
   if (status != 0) {
     // nothing was launched; let the upload finish before the slot's pinned
     // buffer can be overwritten by the next submit
@@ -243,7 +255,9 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
 // through the full-table kernels: max_k is the chain length 11 * N reserved
 inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::none()) {
   return submit_with(
-      wva_launch_solve_scv, problems, max_k, scv, "no kernel geometry holds a chain of length ",
+      [](const double *prob, const double *scv_vec, const double *, double *out, int n, int len,
+         void *stream) { return wva_launch_solve_scv(prob, scv_vec, out, n, len, stream); },
+      problems, max_k, scv, "no kernel geometry holds a chain of length ",
       " in LDS (max_batch limit ~700); use the CPU path for these problems");
 }
 
@@ -252,8 +266,21 @@ inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::no
 inline int64_t submit_compact(py::array problems, int64_t max_n,
                               py::object scv = py::none()) {
   return submit_with(
-      wva_launch_solve_compact, problems, max_n, scv, "the compact-table kernel cannot hold ",
+      [](const double *prob, const double *scv_vec, const double *, double *out, int n, int len,
+         void *stream) { return wva_launch_solve_compact(prob, scv_vec, out, n, len, stream); },
+      problems, max_n, scv, "the compact-table kernel cannot hold ",
       " states in LDS (max_batch limit ~7800); use the CPU path for these problems");
+}
+
+// through the waiting-time tail kernel: rows sized to a TTFT percentile.
+// tail is the [B] vector of their ttft_tail (required); max_n is the largest
+// max batch N the launch reserves LDS for (11 * N doubles, up to ~700)
+inline int64_t submit_tail(py::array problems, int64_t max_n, py::object tail,
+                           py::object scv = py::none()) {
+  if (tail.is_none()) throw py::type_error("tail must be a float64 array");
+  return submit_with(
+      wva_launch_solve_tail, problems, max_n, scv, "the tail kernel cannot hold the tables of ",
+      " states in LDS (max_batch limit ~700); use the CPU path for these problems", tail);
 }
 
 inline std::vector<py::ssize_t> result_shape(int64_t rows) {

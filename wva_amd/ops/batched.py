@@ -50,11 +50,37 @@ M/G/1 correction (per-row service-time cs^2; ``valid_scv`` here):
 
 No vector, or a vector of all 1.0, gives results bit-identical to the
 Markovian ones on every path.
+
+TTFT percentile (per-row waiting-time tail; ``valid_tail`` here):
+
+- a sizing row may carry ``ttft_tail = eps``, the allowed probability that
+  TTFT exceeds ``target_ttft`` (p95 is ``eps = 0.05``);
+- ``eps = 0`` means "mean TTFT": the search compares the mean TTFT with the
+  target, as it always did;
+- for ``eps > 0`` the TTFT search runs on ``y(lam) = P(W > t(lam))`` against
+  the target value ``eps``, with ``t(lam) = (target_ttft -
+  prefill(eff_conc(lam))) / wait_scale`` and ``y = 1`` when ``t <= 0``;
+  ``QueueAnalyzer.wait_exceedance`` is the definition of ``P(W > t)``;
+- the ITL search, the TPS back-off, the replica count and the final
+  evaluation do not change, and ``R_TTFT`` stays the predicted *mean* TTFT
+  at the final rate: only lam* moves, and through it the replica count;
+- ``eps`` must be finite with ``0 <= eps < 1``; any other value gives the
+  all-zero result row in every implementation;
+- a row with ``target_ttft = 0`` ignores a valid ``eps``;
+- the layouts do not change: ``eps`` travels as a separate optional float64
+  vector of length B, like ``scv``.
+
+No vector, or a vector of all 0, gives results bit-identical to the ones
+without it on every path.  On the GPU the rows with ``eps > 0`` and a TTFT
+target run on the waiting-time tail kernel (``submit_tail``, N up to
+GPU_MAX_BATCH_LIMIT), a second launch next to the one every other row takes
+unchanged; such rows with a larger N go to the native CPU solver.
 """
 
 from __future__ import annotations
 
 import contextlib
+import copy
 import math
 import os
 from typing import Dict, List, Optional, Tuple
@@ -70,6 +96,8 @@ from ..analyzer import (
     RequestSize,
     ServiceParms,
     TargetPerf,
+    configured_ttft_tail,
+    percentile_ttft_tail,
 )
 from ..config import MAX_QUEUE_TO_BATCH_RATIO
 from ..core import Allocation, System
@@ -119,16 +147,24 @@ def valid_scv(scv: np.ndarray) -> np.ndarray:
         return np.isfinite(scv) & (scv >= 0)
 
 
-def _scv_vector(scv, n_rows: int) -> np.ndarray:
-    """An explicit ``scv`` — a scalar for the whole batch or a float64
-    ``[B]`` array — as the C-contiguous float64 ``[B]`` vector the native
-    bindings take.  An array of another dtype or shape raises, as the
-    bindings do."""
+def valid_tail(ttft_tail: np.ndarray) -> np.ndarray:
+    """Boolean mask of the TTFT tail probabilities a row may carry: finite
+    with 0 <= eps < 1 (the ``tail_eps`` part of ``row_valid`` in
+    csrc/queue_core.h)."""
+    with np.errstate(invalid="ignore"):
+        return (ttft_tail >= 0) & (ttft_tail < 1)
+
+
+def _scv_vector(scv, n_rows: int, name: str = "scv") -> np.ndarray:
+    """An explicit ``scv`` (or ``ttft_tail``) — a scalar for the whole batch
+    or a float64 ``[B]`` array — as the C-contiguous float64 ``[B]`` vector
+    the native bindings take.  An array of another dtype or shape raises, as
+    the bindings do."""
     if isinstance(scv, np.ndarray) and scv.ndim > 0:
         if scv.dtype != np.float64:
-            raise TypeError(f"scv must be float64, got {scv.dtype}")
+            raise TypeError(f"{name} must be float64, got {scv.dtype}")
         if scv.shape != (n_rows,):
-            raise ValueError(f"scv must be a scalar or [B] = [{n_rows}], got {scv.shape}")
+            raise ValueError(f"{name} must be a scalar or [B] = [{n_rows}], got {scv.shape}")
         return np.ascontiguousarray(scv)
     return np.full(n_rows, float(scv), dtype=np.float64)
 
@@ -303,21 +339,102 @@ class _LargeNTicket:
         return out
 
 
+class _TailTicket:
+    """One chunk split by TTFT functional (a ``ttft_tail`` vector), in flight.
+
+    - valid rows with ``eps > 0``, a TTFT target and N <= GPU_MAX_BATCH_LIMIT
+      went to ``native.submit_tail``, enqueued first;
+    - every other row went to ``submit_rest`` without a vector: today's
+      route, with today's max_k and geometry pick, bit for bit (a row whose
+      eps is invalid rides along and is zeroed in the merge);
+    - tail rows with a larger N (all tail rows under ``WVA_GPU_GRAPH=1``)
+      were solved by the native CPU solver while the launches ran.
+
+    Each part carried the cs^2 of its own rows.  ``collect`` waits for every
+    part and merges them back in row order."""
+
+    def __init__(self, native, device, problems, tail_arr, scv_arr, submit_rest, collect_rest):
+        self.native = native
+        self.n_rows = problems.shape[0]
+        self.collect_rest = collect_rest
+        self.bad = ~valid_tail(tail_arr)
+        with np.errstate(invalid="ignore"):
+            wants = valid_rows(problems) & ~self.bad & (tail_arr > 0)
+            wants &= problems[:, P_TARGET_TTFT] > 0
+            on_kernel = wants & (problems[:, P_MAX_BATCH] <= GPU_MAX_BATCH_LIMIT)
+        if _graph_requested():
+            on_kernel = np.zeros_like(wants)
+        self.on_kernel, self.on_cpu, self.rest = on_kernel, wants & ~on_kernel, ~wants
+        self.kernel_ticket = self.rest_ticket = self.cpu_solved = None
+
+        def part(mask):
+            rows = np.ascontiguousarray(problems[mask])
+            return rows, (None if scv_arr is None else np.ascontiguousarray(scv_arr[mask]))
+
+        try:
+            if on_kernel.any():
+                rows, scv = part(on_kernel)
+                max_n = int(rows[:, P_MAX_BATCH].max())
+                args = (rows, max_n, np.ascontiguousarray(tail_arr[on_kernel]))
+                with _on_device(device):
+                    self.kernel_ticket = native.submit_tail(*(args if scv is None else args + (scv,)))
+            if self.rest.any():
+                self.rest_ticket = submit_rest(*part(self.rest))
+            if self.on_cpu.any():
+                rows, scv = part(self.on_cpu)
+                extra = {} if scv is None else {"scv": scv}
+                self.cpu_solved = solve_problems(
+                    rows, device="cpu", ttft_tail=np.ascontiguousarray(tail_arr[self.on_cpu]), **extra
+                )
+        except BaseException:
+            # a launch already enqueued must not keep its slot for good
+            try:
+                self.collect()
+            except Exception:
+                pass
+            raise
+
+    def collect(self) -> np.ndarray:
+        out = np.zeros((self.n_rows, RESULT_FIELDS), dtype=np.float64)
+        kernel_ticket, self.kernel_ticket = self.kernel_ticket, None
+        rest_ticket, self.rest_ticket = self.rest_ticket, None
+        error = None
+        try:  # both tickets are collected, whatever happens
+            if rest_ticket is not None:
+                out[self.rest] = self.collect_rest(rest_ticket)
+        except Exception as e:  # pragma: no cover - needs a failing GPU
+            error = e
+        try:
+            if kernel_ticket is not None:
+                out[self.on_kernel] = self.native.collect(kernel_ticket)
+        except Exception as e:  # pragma: no cover - needs a failing GPU
+            error = error or e
+        if error is not None:
+            raise error
+        if self.cpu_solved is not None:
+            out[self.on_cpu] = self.cpu_solved
+        out[self.bad] = 0.0
+        return out
+
+
 def _valid_batch_limits(problems: np.ndarray) -> np.ndarray:
     """Column N with the invalid rows' entries replaced by 1, so that they
     neither size a launch nor leave the GPU."""
     return np.where(valid_rows(problems), problems[:, P_MAX_BATCH], 1.0)
 
 
-def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
+def _solve_problems_python(problems: np.ndarray, scv=1.0, ttft_tail=0.0) -> np.ndarray:
     """Reference-semantics scalar fallback via the Python analyzer.
 
     ``scv`` is the service-time cs^2 — a scalar for the whole batch or a
     per-row float64 array (mg1 auto mode derives one per server); a row
-    whose cs^2 fails ``valid_scv`` yields the all-zero row."""
+    whose cs^2 fails ``valid_scv`` yields the all-zero row.  ``ttft_tail``
+    is the TTFT tail probability, a scalar or per-row likewise; a row whose
+    value fails ``valid_tail`` yields the all-zero row."""
     scv_arr = _scv_vector(scv, problems.shape[0])
+    tail_arr = _scv_vector(ttft_tail, problems.shape[0], "ttft_tail")
     out = np.zeros((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
-    valid = valid_rows(problems) & valid_scv(scv_arr)
+    valid = valid_rows(problems) & valid_scv(scv_arr) & valid_tail(tail_arr)
     for i, row in enumerate(problems):
         if not valid[i]:
             continue  # all-zero row; also keeps int() off NaN and inf
@@ -344,6 +461,7 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
                     target_ttft=row[P_TARGET_TTFT],
                     target_itl=row[P_TARGET_ITL],
                     target_tps=row[P_TARGET_TPS],
+                    ttft_tail=float(tail_arr[i]),
                 )
             )
             rate_star = metrics.throughput
@@ -365,7 +483,7 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0) -> np.ndarray:
 
 def solve_problems(
     problems: np.ndarray, device: Optional[str] = None, scv=None,
-    large_n: Optional[bool] = None,
+    large_n: Optional[bool] = None, ttft_tail=None,
 ) -> np.ndarray:
     """Solve a [B, 12] problem matrix -> [B, 6] results.
 
@@ -387,6 +505,15 @@ def solve_problems(
     asks the environment (``WVA_GPU_LARGE_N=1``), ``False`` forces the CPU
     split.  Off by default; no effect on the CPU, on rows within
     GPU_MAX_BATCH_LIMIT, or under ``WVA_GPU_GRAPH=1``.
+
+    ttft_tail: None, or the TTFT tail probability of the percentile sizing
+    (module docstring) — a scalar for the whole batch or a float64 ``[B]``
+    array.  None and all zeros are the mean TTFT, on today's routes.
+    Otherwise, on the GPU, the rows with ``eps > 0``, a TTFT target and N <=
+    GPU_MAX_BATCH_LIMIT run on the waiting-time tail kernel, a second launch
+    enqueued before the first is collected; tail rows with a larger N (all
+    of them under ``WVA_GPU_GRAPH=1``) go to the native CPU solver, and every
+    other row takes the route it takes without the vector.
     """
     from . import get_native, native_available
 
@@ -394,6 +521,11 @@ def solve_problems(
     if problems.ndim != 2 or problems.shape[1] != PROBLEM_FIELDS:
         raise ValueError(f"problems must be [B, {PROBLEM_FIELDS}]")
     scv_arr = None if scv is None else _scv_vector(scv, problems.shape[0])
+    tail_arr = None
+    if ttft_tail is not None:
+        tail_arr = _scv_vector(ttft_tail, problems.shape[0], "ttft_tail")
+        if not tail_arr.any():
+            tail_arr = None  # all zeros: the mean TTFT, today's routes
     if problems.shape[0] == 0:
         return np.zeros((0, RESULT_FIELDS), dtype=np.float64)
 
@@ -416,9 +548,34 @@ def solve_problems(
                 "WVA_ANALYZER=mg1 (cs^2=%.3g): sizing via the Python "
                 "M/G/1-corrected analyzer instead of the native kernel", scv,
             )
-        return _solve_problems_python(problems, scv=scv)
+        return _solve_problems_python(
+            problems, scv=scv, ttft_tail=0.0 if tail_arr is None else tail_arr
+        )
 
     want_gpu = device is not None and str(device).startswith("cuda")
+    if want_gpu and tail_arr is not None:
+        native = get_native()  # raises loudly if missing on a GPU box
+
+        def submit_rest(rows, rows_scv):
+            """Today's route for the other rows.  Where that is the lean
+            dispatch (no row above GPU_MAX_BATCH_LIMIT, no hipGraph), only its
+            submit half, with the same max_k: both launches are enqueued
+            before either is collected.  Any other route runs on the spot."""
+            extra = () if rows_scv is None else (rows_scv,)
+            max_batch = rows[:, P_MAX_BATCH].max()
+            if max_batch <= GPU_MAX_BATCH_LIMIT and not _graph_requested():
+                max_k = max(int(max_batch), 1) * (1 + MAX_QUEUE_TO_BATCH_RATIO)
+                with _on_device(device):
+                    return native.submit(rows, max_k, *extra), None
+            named = {} if rows_scv is None else {"scv": rows_scv}
+            return None, solve_problems(rows, device, large_n=large_n, **named)
+
+        def collect_rest(ticket):
+            return ticket[1] if ticket[0] is None else native.collect(ticket[0])
+
+        split = _TailTicket(native, device, problems, tail_arr, scv_arr, submit_rest,
+                            collect_rest)
+        return split.collect()
     if want_gpu:
         native = get_native()  # raises loudly if missing on a GPU box
         import torch
@@ -472,6 +629,8 @@ def solve_problems(
         # CPU — plain OpenMP beats at::parallel_for's per-call overhead
         # on this workload (profiles/r01_torchfree_cpu.json) — and it is
         # the only native path in the slim controller image.
+        if tail_arr is not None:
+            return get_native_cpu().solve_allocations(problems, scv_arr, tail_arr)
         if scv_arr is None:
             return get_native_cpu().solve_allocations(problems)
         return get_native_cpu().solve_allocations(problems, scv_arr)
@@ -479,6 +638,12 @@ def solve_problems(
         import torch
 
         native = get_native()
+        if tail_arr is not None:
+            return native.solve_allocations(
+                torch.from_numpy(problems), -1,
+                None if scv_arr is None else torch.from_numpy(scv_arr),
+                torch.from_numpy(tail_arr),
+            ).numpy()
         if scv_arr is None:
             return native.solve_allocations(torch.from_numpy(problems)).numpy()
         return native.solve_allocations(
@@ -487,6 +652,10 @@ def solve_problems(
     from . import warn_if_pure_python_fallback
 
     warn_if_pure_python_fallback()
+    if tail_arr is not None:
+        return _solve_problems_python(
+            problems, scv=1.0 if scv_arr is None else scv_arr, ttft_tail=tail_arr
+        )
     if scv_arr is None:
         return _solve_problems_python(problems)
     return _solve_problems_python(problems, scv=scv_arr)
@@ -504,17 +673,21 @@ class SyncDispatch:
     pipeline on any device.  ``global_scv`` is given when some server may
     need the M/G/1 correction: ``submit`` then resolves the rows' cs^2
     against it and passes the vector on, so the fleet is sized by the same
-    native path as a Markovian one."""
+    native path as a Markovian one.  ``ttft_tail`` > 0 sizes every row to
+    that TTFT tail probability (``solve_problems(..., ttft_tail=...)``)."""
 
-    def __init__(self, device: Optional[str], global_scv: Optional[float] = None) -> None:
+    def __init__(self, device: Optional[str], global_scv: Optional[float] = None,
+                 ttft_tail: float = 0.0) -> None:
         self.device = device
         self.global_scv = global_scv
+        self.ttft_tail = ttft_tail
 
     def submit(self, problems: np.ndarray, scv_rows=None):
+        extra = {"ttft_tail": self.ttft_tail} if self.ttft_tail > 0 else {}
         if self.global_scv is not None:
             scv_arr = _resolved_scv(scv_rows, self.global_scv)
-            return solve_problems(problems, self.device, scv=scv_arr)
-        return solve_problems(problems, self.device)
+            return solve_problems(problems, self.device, scv=scv_arr, **extra)
+        return solve_problems(problems, self.device, **extra)
 
     def collect(self, ticket) -> np.ndarray:
         return ticket
@@ -527,14 +700,38 @@ class NativeGpuDispatch:
     the oversized-N split to the CPU is solved synchronously instead.
     ``global_scv`` is given when some server may need the M/G/1 correction:
     ``submit`` then resolves the rows' cs^2 against it and the vector travels
-    with the rows, into the synchronous split too."""
+    with the rows, into the synchronous split too.  ``ttft_tail`` > 0 sizes
+    every row to that TTFT tail probability: the rows with a TTFT target go
+    to the waiting-time tail kernel as a second launch (``_TailTicket``) and
+    the others through this class's own path, so the chunk stays
+    asynchronous."""
 
-    def __init__(self, native, device: str, global_scv: Optional[float] = None) -> None:
+    def __init__(self, native, device: str, global_scv: Optional[float] = None,
+                 ttft_tail: float = 0.0) -> None:
         self.native = native
         self.device = device
         self.global_scv = global_scv
+        self.ttft_tail = 0.0
+        # the mean-TTFT twin: this dispatch (of this class) without the tail,
+        # for the rows of a split chunk that carry no TTFT target
+        self._mean = copy.copy(self) if ttft_tail > 0 else None
+        self.ttft_tail = ttft_tail
+
+    def _submit_split(self, problems: np.ndarray, scv_rows):
+        """The chunk as a ``_TailTicket``; its other rows go through the
+        mean-TTFT twin (cs^2 values already resolved pass ``_resolved_scv``
+        unchanged)."""
+        mean = self._mean
+        scv_arr = None
+        if self.global_scv is not None:
+            scv_arr = _resolved_scv(scv_rows, self.global_scv)
+        tail_arr = np.full(problems.shape[0], self.ttft_tail, dtype=np.float64)
+        return _TailTicket(self.native, self.device, problems, tail_arr, scv_arr,
+                           mean.submit, mean.collect), None
 
     def submit(self, problems: np.ndarray, scv_rows=None):
+        if self.ttft_tail > 0:
+            return self._submit_split(problems, scv_rows)
         scv_arr = None
         if self.global_scv is not None:
             scv_arr = _resolved_scv(scv_rows, self.global_scv)
@@ -553,6 +750,8 @@ class NativeGpuDispatch:
         native_ticket, solved = ticket
         if native_ticket is None:
             return solved
+        if isinstance(native_ticket, _TailTicket):
+            return native_ticket.collect()
         return self.native.collect(native_ticket)
 
 
@@ -566,6 +765,8 @@ class LargeNGpuDispatch(NativeGpuDispatch):
     always did."""
 
     def submit(self, problems: np.ndarray, scv_rows=None):
+        if self.ttft_tail > 0:
+            return self._submit_split(problems, scv_rows)
         if not problems[:, P_MAX_BATCH].max() <= GPU_MAX_BATCH_LIMIT:  # also a NaN N
             batch_limits = _valid_batch_limits(problems)
             if batch_limits.max() > GPU_MAX_BATCH_LIMIT:
@@ -614,15 +815,23 @@ class BatchedAllocationSolver:
     opt-in for servers whose max batch exceeds GPU_MAX_BATCH_LIMIT: their
     rows run on the compact-table kernel and their chunk stays asynchronous
     (``None`` asks ``WVA_GPU_LARGE_N``; no effect off the GPU).
+    ``ttft_percentile`` (in (0, 100), e.g. 95) sizes every server's TTFT
+    target to that percentile of TTFT, not to its mean (module docstring,
+    "TTFT percentile"); ``None`` asks ``WVA_TTFT_PERCENTILE``, read per call
+    and unset by default, the knob ``core.create_allocation`` honours too.
+    On the GPU those rows run on the waiting-time tail kernel and their chunk
+    stays asynchronous.
     """
 
     def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None,
-                 large_n: Optional[bool] = None) -> None:
+                 large_n: Optional[bool] = None,
+                 ttft_percentile: Optional[float] = None) -> None:
         if chunks is not None and chunks < 1:
             raise ValueError("chunks must be at least 1")
         self.device = device
         self.chunks = chunks
         self.large_n = large_n
+        self.ttft_tail = None if ttft_percentile is None else percentile_ttft_tail(ttft_percentile)
 
     def _plan(self, system: System, servers):
         """The dispatch and chunk count for this fleet, decided before any
@@ -634,6 +843,7 @@ class BatchedAllocationSolver:
             s >= 0 and s != 1.0 for s in [getattr(v, "service_scv", -1.0) for v in servers]
         )
         dispatch_scv = global_scv if track_scv else None
+        tail = self.ttft_tail if self.ttft_tail is not None else configured_ttft_tail()
         want_gpu = self.device is not None and str(self.device).startswith("cuda")
         if want_gpu and not _graph_requested():
             from . import get_native
@@ -646,11 +856,11 @@ class BatchedAllocationSolver:
             if len(servers) * len(system.accelerators) >= _GPU_CHUNKING_ROW_BOUND:
                 chunks = 1
             if _large_n_requested(self.large_n):
-                return LargeNGpuDispatch(native, self.device, dispatch_scv), chunks, track_scv
-            return NativeGpuDispatch(native, self.device, dispatch_scv), chunks, track_scv
+                return LargeNGpuDispatch(native, self.device, dispatch_scv, tail), chunks, track_scv
+            return NativeGpuDispatch(native, self.device, dispatch_scv, tail), chunks, track_scv
         if track_scv:
-            return SyncDispatch(self.device, dispatch_scv), 1, True
-        return SyncDispatch(self.device), self.chunks or 1, False
+            return SyncDispatch(self.device, dispatch_scv, tail), 1, True
+        return SyncDispatch(self.device, ttft_tail=tail), self.chunks or 1, False
 
     def calculate(self, system: System) -> None:
         for g in system.accelerators.values():
