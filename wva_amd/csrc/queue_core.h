@@ -79,6 +79,11 @@ constexpr int kMaxQueueToBatchRatio = 10;    // K = (1 + ratio) * N
 //     vector of length B, like scv (absent means 0 for every row).
 // No vector, or a vector of all 0, gives results bit-identical to the ones
 // without it on every path.
+// The tail sum has two evaluations of the same model and window: tail_sum
+// over a log-factorial table (the tail kernel, N <= ~700, and the host
+// solvers), and tail_sum_chunk, the Poisson recurrence without a table (the
+// compact tail kernel, N <= ~7800, and its host reference
+// solve_allocations_tail_compact).  They differ by rounding only.
 enum ProblemField {
   P_ALPHA = 0,    // decode base (ms), >= 0
   P_BETA,         // decode slope (ms per batch unit), >= 0
@@ -519,6 +524,8 @@ struct TailSweep {
   double d;      // ln r
   int J;         // terms of the whole sum
   int lo, hi;    // the window: terms lo..hi
+  int c;         // the window's centre term, min(floor(nu), J - 1)
+  double nu;     // lam t = x r, the Poisson mean (read by the recurrence alone)
 };
 
 // st is the mean-model evaluation at lam and logp_n its log_p(N) (every table
@@ -537,11 +544,13 @@ WVA_HD TailSweep tail_sweep_of(const Parms &p, const Stats &st, double logp_n, d
   w.log_c = logp_n - st.log_ref - log(st.accept_mass) - x;
   w.J = p.max_batch * kMaxQueueToBatchRatio;
   const double top = (double)(w.J - 1);
-  const double c = floor(fmin(lam * t, top));  // nu = x r = lam t
+  w.nu = lam * t;  // nu = x r = lam t
+  const double c = floor(fmin(w.nu, top));
   const double L = 37.54 + 2.0 * log((double)w.J);
   const double h = 2.0 * L + 1.0 + sqrt(2.0 * L * c);
   w.lo = (int)fmax(c - h, 0.0);
   w.hi = (int)fmin(c + h, top);
+  w.c = (int)c;
   return w;
 }
 
@@ -570,6 +579,112 @@ WVA_HD double tail_sum(const TailSweep &w, const LogFact &lf, int first, int str
 // P(W > t) from the reduced tail sum; the clamp only trims rounding
 WVA_HD double tail_probability(const TailSweep &w, double sum) {
   return fmin(fmax(sum / expm1(w.d), 0.0), 1.0);
+}
+
+// ---------------------------------------------------------------------------
+// The tail sum without a log-factorial table: the Poisson weights by their
+// recurrence, over contiguous chunks.  Same model, same window, same result up
+// to rounding; it needs no memory besides the cumulative table, so it holds
+// any N the compact table holds.
+//
+// With e(i) = i a - lf(i) + log_c the term is T_i = exp(e(i)) expm1((J-i) d).
+// The window lo..hi is cut into `parts` contiguous chunks of ceil(window /
+// parts) terms, the last short or empty; a workgroup thread takes chunk tid,
+// the host the one chunk.  A worker forms the weight of its chunk's first
+// term once, relative to the centre term c of the window,
+//
+//   w_i0 = exp(e(i0) - e(c)) = exp((i0 - c) a - (lf(i0) - lf(c))),
+//
+// with lf from the closed form below, and then walks
+//
+//   w_{i+1} = w_i nu / (i + 1),   sum += w_i expm1((J - i) d):
+//
+// one expm1 and one multiply-divide per term, no exp, no table read.  The
+// reduced sum is scaled back by exp(e(c)) (tail_centre_term) before
+// tail_probability.  log_c (ln pi_N - x, as small as it likes) enters only
+// there: inside the window the relative weights lie between about e^-2L
+// (window bound above, L ~ 60) and 1, so none underflows or overflows however
+// small pi_N is.
+//
+// Error.  The chunk's first weight carries the rounding of two lf values and
+// of (i0 - c) a, about 2^-53 (lf(i0) + lf(c) + |i0 - c| a): 2e-10 relative at
+// J = 76800, what the scanned table's entries carry as well.  Each recurrence
+// step adds three roundings (the stride-2 form below), so a chunk of n terms
+// drifts by at most 1.5 n 2^-52: 25 terms per thread at N = 7680 near
+// saturation (a window of ~6300 terms over 256 threads) is 1e-14, and the
+// host's single chunk of 6300 is 2e-12.  Both stay far inside the search's
+// 1e-6 stop and below the first weight's own error.
+// ---------------------------------------------------------------------------
+
+// lf(i) = ln i!, i >= 0, without a table to scan.  Below 16 the correctly
+// rounded values; from 16 on the Stirling series
+//   (i + 1/2) ln i - i + ln(2 pi) / 2 + 1/(12 i) - 1/(360 i^3) + 1/(1260 i^5)
+//   - 1/(1680 i^7) + 1/(1188 i^9).
+// For a positive argument the series alternates around the true value, so the
+// truncation error is below the first omitted term, 691 / (360360 i^11): at
+// most 1.1e-16 at i = 16, where 2^-53 lf(i) = 3.4e-15, and the ratio falls
+// like i^-12 from there.  Measured against 60-digit values for every i <
+// 3000 and every 7th up to 80000, the whole error, rounding included, stays
+// within 3.5e-16 lf(i).  lgamma(i + 1) was the alternative: the host's is no
+// more accurate on the same values (5.1e-16 lf(i)), and inlined into the
+// compact tail kernel the device library's takes it from 159 to 256 vector
+// registers plus 10 AGPRs, that is from 3 waves per SIMD to 1, and from 15.5k
+// to 25.3k lines of assembly (cross-compiled for gfx950, not run).
+WVA_HD double log_factorial(int i) {
+  static constexpr double kSmall[16] = {0.0,
+                                 0.0,
+                                 0.6931471805599453,
+                                 1.791759469228055,
+                                 3.1780538303479458,
+                                 4.787491742782046,
+                                 6.579251212010101,
+                                 8.525161361065415,
+                                 10.60460290274525,
+                                 12.801827480081469,
+                                 15.104412573075516,
+                                 17.502307845873887,
+                                 19.987214495661885,
+                                 22.552163853123425,
+                                 25.19122118273868,
+                                 27.89927138384089};
+  if (i < 16) return kSmall[i < 0 ? 0 : i];
+  const double x = (double)i;
+  const double r = 1.0 / x;
+  const double r2 = r * r;
+  const double series =
+      r * (1.0 / 12.0 +
+           r2 * (-1.0 / 360.0 + r2 * (1.0 / 1260.0 + r2 * (-1.0 / 1680.0 + r2 * (1.0 / 1188.0)))));
+  return (x + 0.5) * log(x) - x + 0.9189385332046727 + series;
+}
+
+// exp(e(c)): what the chunked sums are relative to
+WVA_HD double tail_centre_term(const TailSweep &w) {
+  return exp((double)w.c * w.a - log_factorial(w.c) + w.log_c);
+}
+
+// Chunk `part` of `parts` of the window, relative to the centre term.  Two
+// independent chains per pass, as in the other sweeps: the even and the odd
+// terms of the chunk, each by the recurrence's stride-2 form w_{i+2} = w_i
+// nu^2 / ((i + 1)(i + 2)) (the integer product is exact below 2^53).  Every
+// expm1 factor is negative: the result is <= 0.  0 for an empty chunk.
+WVA_HD double tail_sum_chunk(const TailSweep &w, int part, int parts) {
+  const int len = (w.hi - w.lo + parts) / parts;  // ceil(window / parts)
+  const int i0 = w.lo + part * len;
+  const int end = i0 + len - 1 < w.hi ? i0 + len - 1 : w.hi;
+  if (i0 > end) return 0.0;
+  const double nu2 = w.nu * w.nu;
+  double wa = exp((double)(i0 - w.c) * w.a - (log_factorial(i0) - log_factorial(w.c)));
+  double wb = wa * w.nu / (double)(i0 + 1);
+  double s0 = 0.0, s1 = 0.0;
+  int i = i0;
+  for (; i + 1 <= end; i += 2) {
+    s0 += wa * expm1((double)(w.J - i) * w.d);
+    s1 += wb * expm1((double)(w.J - i - 1) * w.d);
+    wa *= nu2 / ((double)(i + 1) * (double)(i + 2));
+    wb *= nu2 / ((double)(i + 2) * (double)(i + 3));
+  }
+  if (i <= end) s0 += wa * expm1((double)(w.J - i) * w.d);
+  return s0 + s1;
 }
 
 // Whether an evaluator offers exceedance(lam, target_ttft) = P(TTFT > target)

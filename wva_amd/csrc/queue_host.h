@@ -62,6 +62,7 @@ inline double host_exceedance(const Table &table, const double *lf, double cum_l
 
 // K = 11 * N doubles, evaluated inside the significance window (state_window)
 struct HostFullTable {
+  static constexpr bool kReadsLogFactorials = true;
   static int length(const double *pr) { return row_chain_length(pr); }
   const Parms &p;
   const double *cum;
@@ -79,6 +80,7 @@ struct HostFullTable {
 
 // N doubles (queue_core.h, "Compact table"); no window
 struct HostCompactTable {
+  static constexpr bool kReadsLogFactorials = true;
   static int length(const double *pr) { return row_compact_length(pr); }
   const Parms &p;
   const double *cum;
@@ -91,6 +93,23 @@ struct HostCompactTable {
   Stats eval(double lam) const { return eval_model_compact(p, cum, log_mu_n, lam); }
   double exceedance(double lam, double target_ttft) const {
     return host_exceedance(*this, lf, cum[p.max_batch - 1], lam, target_ttft);
+  }
+};
+
+// The compact table with the tail by the Poisson recurrence (queue_core.h,
+// tail_sum_chunk): the window as one chunk, no log-factorial table (the third
+// argument is accepted and ignored, and the bindings fill none).  The mean
+// model is HostCompactTable's, bit for bit; it is the host reference of the
+// compact tail kernel, not a routing target.
+struct HostTailCompactTable : HostCompactTable {
+  static constexpr bool kReadsLogFactorials = false;
+  HostTailCompactTable(const Parms &parms, double *table, const double * = nullptr)
+      : HostCompactTable(parms, table) {}
+  double exceedance(double lam, double target_ttft) const {
+    const double logp_n = (double)p.max_batch * log(lam) - cum[p.max_batch - 1];
+    const TailSweep w = tail_sweep_of(p, eval(lam), logp_n, lam, target_ttft);
+    if (w.certain) return 1.0;
+    return tail_probability(w, tail_centre_term(w) * tail_sum_chunk(w, 0, 1));
   }
 };
 
@@ -128,10 +147,12 @@ inline int batch_table_length(const double *pr, long long rows) {
 }
 
 // Length of the log-factorial table a batch needs: 10 * N of its largest
-// valid row that carries a ttft_tail, 0 without a vector.
+// valid row that carries a ttft_tail, 0 without a vector or for a policy that
+// reads none.
+template <typename Table>
 inline long long batch_tail_length(const double *pr, const double *tail, long long rows) {
   long long longest = 0;
-  if (tail == nullptr) return longest;
+  if (tail == nullptr || !Table::kReadsLogFactorials) return longest;
   for (long long i = 0; i < rows; ++i) {
     const double *row = pr + i * PROBLEM_FIELDS;
     if (!(tail[i] > 0.0) || !row_valid(row)) continue;

@@ -73,7 +73,7 @@ static torch::Tensor solve_on_cpu(const torch::Tensor &problems, const double *s
   const double *pr = problems.data_ptr<double>();
   double *res = out.data_ptr<double>();
   const int table_len = wva::batch_table_length<Table>(pr, B);
-  const std::vector<double> lf = wva::log_factorials(wva::batch_tail_length(pr, tail_ptr, B));
+  const std::vector<double> lf = wva::log_factorials(wva::batch_tail_length<Table>(pr, tail_ptr, B));
   at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
     std::vector<double> cum((size_t)table_len);
     for (int64_t i = begin; i < end; ++i) {
@@ -154,6 +154,20 @@ static torch::Tensor solve_allocations_compact(
                                              scv_data(ttft_tail, problems, "ttft_tail"));
 }
 
+// The compact-table host solve with the waiting-time tail by the Poisson
+// recurrence (queue_core.h, tail_sum_chunk), no log-factorial table: the host
+// reference of the compact tail kernel, which is reached through
+// submit_tail_compact.  CPU tensors only.
+static torch::Tensor solve_allocations_tail_compact(
+    torch::Tensor problems, c10::optional<torch::Tensor> scv = c10::nullopt,
+    c10::optional<torch::Tensor> ttft_tail = c10::nullopt) {
+  check_problems(problems);
+  TORCH_CHECK(!problems.is_cuda(), "solve_allocations_tail_compact takes CPU tensors");
+  problems = problems.contiguous();
+  return solve_on_cpu<wva::HostTailCompactTable>(problems, scv_data(scv, problems),
+                                                 scv_data(ttft_tail, problems, "ttft_tail"));
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "wva_amd native batched queue solver (CPU + gfx950 HIP)";
   m.def("solve_allocations", &solve_allocations,
@@ -162,6 +176,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("scv") = pybind11::none(), pybind11::arg("ttft_tail") = pybind11::none());
   m.def("solve_allocations_compact", &solve_allocations_compact,
         "The same sizing on the CPU over the compact table (N doubles per row)",
+        pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
+        pybind11::arg("ttft_tail") = pybind11::none());
+  m.def("solve_allocations_tail_compact", &solve_allocations_tail_compact,
+        "The compact-table sizing on the CPU with the waiting-time tail by the "
+        "Poisson recurrence, no log-factorial table",
         pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
         pybind11::arg("ttft_tail") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
@@ -187,6 +206,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "percentile, tail the float64 [B] vector of their ttft_tail; max_n is "
         "the largest max batch N the launch reserves LDS for (11 * N doubles, "
         "up to 700); same slot pool, stream, checks and collect as submit",
+        pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("tail"),
+        pybind11::arg("scv") = pybind11::none());
+  m.def("submit_tail_compact", &wva::dispatch::submit_tail_compact,
+        "submit through the compact waiting-time tail kernel: rows sized to a "
+        "TTFT percentile without a log-factorial table, tail the float64 [B] "
+        "vector of their ttft_tail; max_n is the largest max batch N the launch "
+        "reserves LDS for (N doubles, up to ~7800); same slot pool, stream, "
+        "checks and collect as submit",
         pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("tail"),
         pybind11::arg("scv") = pybind11::none());
   m.def("collect", &wva::dispatch::collect,

@@ -19,7 +19,8 @@ namespace py = pybind11;
 
 // One body for both table policies of queue_host.h: the full table
 // (solve_allocations) and the compact one, N doubles of scratch per row
-// instead of 11 * N (solve_allocations_compact).  scv, ttft_tail: scv_arg.h.
+// instead of 11 * N (solve_allocations_compact), and the compact one with the
+// table-free tail (solve_allocations_tail_compact).  scv, ttft_tail: scv_arg.h.
 template <typename Table>
 static py::array_t<double> solve_allocations(
     py::array_t<double, py::array::c_style | py::array::forcecast> problems,
@@ -39,7 +40,7 @@ static py::array_t<double> solve_allocations(
 
   const int table_len = wva::batch_table_length<Table>(pr, B);
   const std::vector<double> lf =
-      wva::log_factorials(wva::batch_tail_length(pr, tail_ptr, B));
+      wva::log_factorials(wva::batch_tail_length<Table>(pr, tail_ptr, B));
   {
     py::gil_scoped_release release;
 #pragma omp parallel
@@ -63,6 +64,12 @@ PYBIND11_MODULE(_queue_native_cpu, m) {
         py::arg("scv") = py::none(), py::arg("ttft_tail") = py::none());
   m.def("solve_allocations_compact", &solve_allocations<wva::HostCompactTable>,
         "The same sizing over the compact table (N doubles per row)",
+        py::arg("problems"), py::arg("scv") = py::none(),
+        py::arg("ttft_tail") = py::none());
+  m.def("solve_allocations_tail_compact", &solve_allocations<wva::HostTailCompactTable>,
+        "The compact-table sizing with the waiting-time tail by the Poisson "
+        "recurrence, no log-factorial table: the host reference of the compact "
+        "tail kernel",
         py::arg("problems"), py::arg("scv") = py::none(),
         py::arg("ttft_tail") = py::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;

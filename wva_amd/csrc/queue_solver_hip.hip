@@ -62,8 +62,10 @@ namespace wva {
 // The launcher auto-selects (occupancy-aware, see wva_launch_solve_scv);
 // WVA_GPU_THREADS=64|128|256|384|896 overrides, read per launch.  A sixth
 // kernel runs the 256 body over the compact table (N doubles, not 11*N), and
-// a seventh sizes rows to a TTFT percentile (the waiting-time tail kernel at
-// the end of the namespace: compact table plus a log-factorial table).
+// a seventh sizes rows to a TTFT percentile (the waiting-time tail kernel near
+// the end of the namespace: compact table plus a log-factorial table), and an
+// eighth does so without the second table, for N up to the compact limit (the
+// compact waiting-time tail kernel at the end of the namespace).
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -903,6 +905,72 @@ extern "C" __global__ void __launch_bounds__(kTailThreads) wva_solve_kernel_tail
   solve_body<kTailThreads, LdsCompactTable, TailRows>(prob, scv, out, n_problems, max_n, tail);
 }
 
+// ---------------------------------------------------------------------------
+// Compact waiting-time tail kernel: percentile rows at any N the compact
+// table holds (up to ~7800).  The same model, window and row contract as the
+// tail kernel above; the tail sum runs on the Poisson recurrence
+// (queue_core.h, tail_sum_chunk) and needs no log-factorial table.
+//
+// LDS (doubles): cum[max_n], totals[256], and of the 64 slack doubles red[20]
+// and tail_red[4]: max_n + 256 + 64, the compact kernel's footprint.  One
+// scan (build_cum); after it the tail reads nothing from LDS but the partials.
+//
+// One evaluation of y(lam):
+//   - the mean-model sums, WgEval<256, LdsCompactTable>::eval (two barriers);
+//   - tail_sweep_of: window, centre term and nu, uniform over the workgroup;
+//   - thread tid takes the window's tid-th contiguous chunk of ceil(window /
+//     256) terms: two closed-form ln i! and one exp for the chunk's first
+//     weight, then one expm1 and one multiply-divide per term in registers
+//     (two independent chains).  A window shorter than 256 terms leaves the
+//     threads behind it an empty chunk and a zero partial;
+//   - the __shfl_down reduction, one barrier for tail_red, and the scaling by
+//     the centre term, which every thread computes for itself (uniform).
+// tail_red is apart from red for the reason given above: that barrier is the
+// only one the tail adds.
+// ---------------------------------------------------------------------------
+struct WgTailCompactEval {
+  static constexpr int WAVES = kTailThreads / 64;
+  const Parms &p;
+  WgEval<kTailThreads, LdsCompactTable> mean;
+  double *tail_red;  // LDS, WAVES
+
+  __device__ Stats eval(double lam) const { return mean.eval(lam); }
+
+  __device__ double exceedance(double lam, double target_ttft) const {
+    const Stats st = mean.eval(lam);
+    const double logp_n = mean.table.log_p(log(lam), p.max_batch);
+    const TailSweep w = tail_sweep_of(p, st, logp_n, lam, target_ttft);
+    if (w.certain) return 1.0;  // uniform: st is the same on every thread
+    double sum = tail_sum_chunk(w, (int)threadIdx.x, kTailThreads);
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    if ((threadIdx.x & 63) == 0) tail_red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    sum = 0.0;
+    for (int wv = 0; wv < WAVES; ++wv) sum += tail_red[wv];
+    return tail_probability(w, tail_centre_term(w) * sum);
+  }
+};
+
+// solve_body's row policy of the compact tail kernel: the row's eps from the
+// launch's vector, cum[max_n] alone reserved, nothing to scan.
+struct TailCompactRows {
+  static __device__ double eps(const double *tail, int pid) { return tail[pid]; }
+  static __device__ int table_doubles(int max_n) { return max_n; }
+  template <int THREADS, typename Table>
+  static __device__ WgTailCompactEval evaluator(const Parms &p, const Table &table, double *,
+                                                double *, double *red) {
+    static_assert(THREADS == kTailThreads, "the tail evaluator is a 256-thread one");
+    return {p, {p, table, red}, red + 5 * WgTailCompactEval::WAVES};
+  }
+};
+
+extern "C" __global__ void __launch_bounds__(kTailThreads) wva_solve_kernel_tail_compact(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    const double *__restrict__ tail, double *__restrict__ out, int n_problems, int max_n) {
+  solve_body<kTailThreads, LdsCompactTable, TailCompactRows>(prob, scv, out, n_problems, max_n,
+                                                             tail);
+}
+
 }  // namespace wva
 
 #include <cstdlib>
@@ -1004,5 +1072,20 @@ extern "C" int wva_launch_solve_tail(const double *prob, const double *scv, cons
   const size_t smem = (size_t)(table_len + wva::kTailThreads + 64) * sizeof(double);
   hipLaunchKernelGGL(wva::wva_solve_kernel_tail, dim3(n_problems), dim3(wva::kTailThreads), smem,
                      (hipStream_t)stream, prob, scv, tail, out, n_problems, max_n);
+  return (int)hipGetLastError();
+}
+
+// Compact waiting-time tail launch: tail as above, max_n the largest trunc(N)
+// the launch reserves LDS for, cum[max_n] alone.  -1, and nothing launched,
+// without a tail vector or when max_n + 256 + 64 doubles exceed 64 KiB
+// (max_n beyond 7872).
+extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *scv,
+                                             const double *tail, double *out, int n_problems,
+                                             int max_n, void *stream) {
+  if (tail == nullptr || max_n < 1 || !fits_lds(max_n, wva::kTailThreads)) return -1;
+  const size_t smem = (size_t)(max_n + wva::kTailThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_solve_kernel_tail_compact, dim3(n_problems),
+                     dim3(wva::kTailThreads), smem, (hipStream_t)stream, prob, scv, tail, out,
+                     n_problems, max_n);
   return (int)hipGetLastError();
 }

@@ -22,8 +22,8 @@
 // the B rows, so the one upload copy moves both and nothing is created per
 // call.  A submit without one uploads the rows alone and launches with a
 // null vector: whatever an earlier submit left behind the rows of a reused
-// slot is never read.  A submit_tail carries one more vector, the rows'
-// ttft_tail, behind that, in the same upload.
+// slot is never read.  A submit_tail or submit_tail_compact carries one more
+// vector, the rows' ttft_tail, behind that, in the same upload.
 //
 // Buffers live in a pool of slots, each with pinned in/out, device in/out
 // and an event created with hipEventDisableTiming.  Slots are grow-only;
@@ -63,6 +63,9 @@ extern "C" int wva_launch_solve_compact(const double *prob, const double *scv, d
                                         int n_problems, int max_n, void *stream);
 extern "C" int wva_launch_solve_tail(const double *prob, const double *scv, const double *tail,
                                      double *out, int n_problems, int max_n, void *stream);
+extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *scv,
+                                             const double *tail, double *out, int n_problems,
+                                             int max_n, void *stream);
 
 namespace wva {
 namespace dispatch {
@@ -281,6 +284,18 @@ inline int64_t submit_tail(py::array problems, int64_t max_n, py::object tail,
   return submit_with(
       wva_launch_solve_tail, problems, max_n, scv, "the tail kernel cannot hold the tables of ",
       " states in LDS (max_batch limit ~700); use the CPU path for these problems", tail);
+}
+
+// through the compact waiting-time tail kernel: the same rows and vector as
+// submit_tail, the tail sum by the Poisson recurrence; max_n is the largest
+// max batch N the launch reserves LDS for (N doubles, up to ~7800)
+inline int64_t submit_tail_compact(py::array problems, int64_t max_n, py::object tail,
+                                   py::object scv = py::none()) {
+  if (tail.is_none()) throw py::type_error("tail must be a float64 array");
+  return submit_with(
+      wva_launch_solve_tail_compact, problems, max_n, scv,
+      "the compact tail kernel cannot hold ",
+      " states in LDS (max_batch limit ~7800); use the CPU path for these problems", tail);
 }
 
 inline std::vector<py::ssize_t> result_shape(int64_t rows) {

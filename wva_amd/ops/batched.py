@@ -74,7 +74,18 @@ No vector, or a vector of all 0, gives results bit-identical to the ones
 without it on every path.  On the GPU the rows with ``eps > 0`` and a TTFT
 target run on the waiting-time tail kernel (``submit_tail``, N up to
 GPU_MAX_BATCH_LIMIT), a second launch next to the one every other row takes
-unchanged; such rows with a larger N go to the native CPU solver.
+unchanged.  Such rows with a larger N go to the native CPU solver, unless the
+``large_n`` opt-in is on: then those up to GPU_COMPACT_MAX_BATCH_LIMIT run on
+the compact waiting-time tail kernel (``submit_tail_compact``: the same model
+and window, the tail sum by the Poisson recurrence instead of a log-factorial
+table), one more launch enqueued before any is collected.  Routes of a GPU
+solve with a ``ttft_tail`` vector:
+
+- eps > 0, target_ttft > 0, N <= 700: ``submit_tail``;
+- the same with 700 < N <= 7680, ``large_n`` on, not under ``WVA_GPU_GRAPH=1``:
+  ``submit_tail_compact``;
+- the same with ``large_n`` off (the default), or N > 7680: native CPU solver;
+- every other row: the route it takes without the vector.
 """
 
 from __future__ import annotations
@@ -344,16 +355,21 @@ class _TailTicket:
 
     - valid rows with ``eps > 0``, a TTFT target and N <= GPU_MAX_BATCH_LIMIT
       went to ``native.submit_tail``, enqueued first;
+    - with ``large_n`` (the opt-in, already resolved by the caller), such rows
+      with GPU_MAX_BATCH_LIMIT < N <= GPU_COMPACT_MAX_BATCH_LIMIT went to
+      ``native.submit_tail_compact``, one more launch enqueued right behind;
     - every other row went to ``submit_rest`` without a vector: today's
       route, with today's max_k and geometry pick, bit for bit (a row whose
       eps is invalid rides along and is zeroed in the merge);
-    - tail rows with a larger N (all tail rows under ``WVA_GPU_GRAPH=1``)
-      were solved by the native CPU solver while the launches ran.
+    - the remaining tail rows (N above the limit of the launches allowed; all
+      tail rows under ``WVA_GPU_GRAPH=1``) were solved by the native CPU
+      solver while the launches ran.
 
     Each part carried the cs^2 of its own rows.  ``collect`` waits for every
     part and merges them back in row order."""
 
-    def __init__(self, native, device, problems, tail_arr, scv_arr, submit_rest, collect_rest):
+    def __init__(self, native, device, problems, tail_arr, scv_arr, submit_rest, collect_rest,
+                 large_n=False):
         self.native = native
         self.n_rows = problems.shape[0]
         self.collect_rest = collect_rest
@@ -362,22 +378,31 @@ class _TailTicket:
             wants = valid_rows(problems) & ~self.bad & (tail_arr > 0)
             wants &= problems[:, P_TARGET_TTFT] > 0
             on_kernel = wants & (problems[:, P_MAX_BATCH] <= GPU_MAX_BATCH_LIMIT)
+            on_compact = wants & ~on_kernel & (problems[:, P_MAX_BATCH] <= GPU_COMPACT_MAX_BATCH_LIMIT)
         if _graph_requested():
             on_kernel = np.zeros_like(wants)
-        self.on_kernel, self.on_cpu, self.rest = on_kernel, wants & ~on_kernel, ~wants
-        self.kernel_ticket = self.rest_ticket = self.cpu_solved = None
+        if not large_n or _graph_requested():
+            on_compact = np.zeros_like(wants)
+        self.on_kernel, self.on_compact, self.rest = on_kernel, on_compact, ~wants
+        self.on_cpu = wants & ~on_kernel & ~on_compact
+        self.kernel_ticket = self.compact_ticket = self.rest_ticket = self.cpu_solved = None
 
         def part(mask):
             rows = np.ascontiguousarray(problems[mask])
             return rows, (None if scv_arr is None else np.ascontiguousarray(scv_arr[mask]))
 
+        def submit_tail_rows(submit, mask):
+            rows, scv = part(mask)
+            max_n = int(rows[:, P_MAX_BATCH].max())
+            args = (rows, max_n, np.ascontiguousarray(tail_arr[mask]))
+            with _on_device(device):
+                return submit(*(args if scv is None else args + (scv,)))
+
         try:
             if on_kernel.any():
-                rows, scv = part(on_kernel)
-                max_n = int(rows[:, P_MAX_BATCH].max())
-                args = (rows, max_n, np.ascontiguousarray(tail_arr[on_kernel]))
-                with _on_device(device):
-                    self.kernel_ticket = native.submit_tail(*(args if scv is None else args + (scv,)))
+                self.kernel_ticket = submit_tail_rows(native.submit_tail, on_kernel)
+            if on_compact.any():
+                self.compact_ticket = submit_tail_rows(native.submit_tail_compact, on_compact)
             if self.rest.any():
                 self.rest_ticket = submit_rest(*part(self.rest))
             if self.on_cpu.any():
@@ -397,18 +422,20 @@ class _TailTicket:
     def collect(self) -> np.ndarray:
         out = np.zeros((self.n_rows, RESULT_FIELDS), dtype=np.float64)
         kernel_ticket, self.kernel_ticket = self.kernel_ticket, None
+        compact_ticket, self.compact_ticket = self.compact_ticket, None
         rest_ticket, self.rest_ticket = self.rest_ticket, None
         error = None
-        try:  # both tickets are collected, whatever happens
+        try:  # every ticket is collected, whatever happens
             if rest_ticket is not None:
                 out[self.rest] = self.collect_rest(rest_ticket)
         except Exception as e:  # pragma: no cover - needs a failing GPU
             error = e
-        try:
-            if kernel_ticket is not None:
-                out[self.on_kernel] = self.native.collect(kernel_ticket)
-        except Exception as e:  # pragma: no cover - needs a failing GPU
-            error = error or e
+        for mask, ticket in ((self.on_kernel, kernel_ticket), (self.on_compact, compact_ticket)):
+            try:
+                if ticket is not None:
+                    out[mask] = self.native.collect(ticket)
+            except Exception as e:  # pragma: no cover - needs a failing GPU
+                error = error or e
         if error is not None:
             raise error
         if self.cpu_solved is not None:
@@ -504,16 +531,19 @@ def solve_problems(
     launch, enqueued together with the first) instead of the CPU.  ``None``
     asks the environment (``WVA_GPU_LARGE_N=1``), ``False`` forces the CPU
     split.  Off by default; no effect on the CPU, on rows within
-    GPU_MAX_BATCH_LIMIT, or under ``WVA_GPU_GRAPH=1``.
+    GPU_MAX_BATCH_LIMIT, or under ``WVA_GPU_GRAPH=1``.  It covers percentile
+    rows (``ttft_tail``) as well: those run on the compact tail kernel.
 
     ttft_tail: None, or the TTFT tail probability of the percentile sizing
     (module docstring) — a scalar for the whole batch or a float64 ``[B]``
     array.  None and all zeros are the mean TTFT, on today's routes.
     Otherwise, on the GPU, the rows with ``eps > 0``, a TTFT target and N <=
     GPU_MAX_BATCH_LIMIT run on the waiting-time tail kernel, a second launch
-    enqueued before the first is collected; tail rows with a larger N (all
-    of them under ``WVA_GPU_GRAPH=1``) go to the native CPU solver, and every
-    other row takes the route it takes without the vector.
+    enqueued before the first is collected; tail rows with a larger N go to
+    the compact tail kernel up to GPU_COMPACT_MAX_BATCH_LIMIT when ``large_n``
+    is on and to the native CPU solver otherwise (all tail rows under
+    ``WVA_GPU_GRAPH=1``), and every other row takes the route it takes
+    without the vector.
     """
     from . import get_native, native_available
 
@@ -574,7 +604,7 @@ def solve_problems(
             return ticket[1] if ticket[0] is None else native.collect(ticket[0])
 
         split = _TailTicket(native, device, problems, tail_arr, scv_arr, submit_rest,
-                            collect_rest)
+                            collect_rest, large_n=_large_n_requested(large_n))
         return split.collect()
     if want_gpu:
         native = get_native()  # raises loudly if missing on a GPU box
@@ -704,7 +734,8 @@ class NativeGpuDispatch:
     every row to that TTFT tail probability: the rows with a TTFT target go
     to the waiting-time tail kernel as a second launch (``_TailTicket``) and
     the others through this class's own path, so the chunk stays
-    asynchronous."""
+    asynchronous; a tail row above GPU_MAX_BATCH_LIMIT is solved on the CPU
+    inside ``submit``."""
 
     def __init__(self, native, device: str, global_scv: Optional[float] = None,
                  ttft_tail: float = 0.0) -> None:
@@ -717,17 +748,18 @@ class NativeGpuDispatch:
         self._mean = copy.copy(self) if ttft_tail > 0 else None
         self.ttft_tail = ttft_tail
 
-    def _submit_split(self, problems: np.ndarray, scv_rows):
+    def _submit_split(self, problems: np.ndarray, scv_rows, large_n: bool = False):
         """The chunk as a ``_TailTicket``; its other rows go through the
         mean-TTFT twin (cs^2 values already resolved pass ``_resolved_scv``
-        unchanged)."""
+        unchanged).  ``large_n``: whether a percentile row above
+        GPU_MAX_BATCH_LIMIT goes to ``submit_tail_compact``, not to the CPU."""
         mean = self._mean
         scv_arr = None
         if self.global_scv is not None:
             scv_arr = _resolved_scv(scv_rows, self.global_scv)
         tail_arr = np.full(problems.shape[0], self.ttft_tail, dtype=np.float64)
         return _TailTicket(self.native, self.device, problems, tail_arr, scv_arr,
-                           mean.submit, mean.collect), None
+                           mean.submit, mean.collect, large_n=large_n), None
 
     def submit(self, problems: np.ndarray, scv_rows=None):
         if self.ttft_tail > 0:
@@ -759,14 +791,17 @@ class LargeNGpuDispatch(NativeGpuDispatch):
     """NativeGpuDispatch under the ``large_n`` opt-in (``solve_problems``):
     a chunk with a valid row above GPU_MAX_BATCH_LIMIT stays asynchronous, its
     rows up to GPU_COMPACT_MAX_BATCH_LIMIT going to the compact-table kernel
-    as a second launch (``_LargeNTicket``).  Any other chunk takes the parent
-    class's path unchanged.  ``BatchedAllocationSolver`` picks this class only
-    when the opt-in is on, so the default pipeline runs the class above as it
-    always did."""
+    as a second launch (``_LargeNTicket``).  Under ``ttft_tail`` > 0 the
+    chunk's ``_TailTicket`` carries the opt-in: percentile rows up to
+    GPU_COMPACT_MAX_BATCH_LIMIT go to the compact tail kernel
+    (``submit_tail_compact``), so that chunk stays asynchronous too.  Any
+    other chunk takes the parent class's path unchanged.
+    ``BatchedAllocationSolver`` picks this class only when the opt-in is on,
+    so the default pipeline runs the class above as it always did."""
 
     def submit(self, problems: np.ndarray, scv_rows=None):
         if self.ttft_tail > 0:
-            return self._submit_split(problems, scv_rows)
+            return self._submit_split(problems, scv_rows, large_n=True)
         if not problems[:, P_MAX_BATCH].max() <= GPU_MAX_BATCH_LIMIT:  # also a NaN N
             batch_limits = _valid_batch_limits(problems)
             if batch_limits.max() > GPU_MAX_BATCH_LIMIT:
@@ -820,7 +855,8 @@ class BatchedAllocationSolver:
     "TTFT percentile"); ``None`` asks ``WVA_TTFT_PERCENTILE``, read per call
     and unset by default, the knob ``core.create_allocation`` honours too.
     On the GPU those rows run on the waiting-time tail kernel and their chunk
-    stays asynchronous.
+    stays asynchronous; with ``large_n`` that holds for servers whose max
+    batch exceeds GPU_MAX_BATCH_LIMIT too (the compact tail kernel).
     """
 
     def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None,
