@@ -16,9 +16,13 @@ Ordering invariants preserved exactly:
   cost/value by the replica factor (greedy.go:208-211,299-310).
 
 solve_greedy runs the solve itself in C++ (csrc/greedy_core.h) when an
-extension carries it: _marshal lays the problem out as flat arrays, the
-binding returns the chosen allocation and the granted replicas per server,
-and _apply sets them, rescaling partial grants in Python floats.  The Python
+extension carries it: the binding reads the candidates' fields from the
+servers' Allocation objects itself (_solve_objects) and returns the chosen
+allocation and the granted replicas per server, and _apply sets them,
+rescaling partial grants in Python floats.  Whatever that entry point does
+not take (an Allocation subclass, a numpy scalar, a bound) goes to _marshal,
+which lays the problem out as flat arrays or sends it on to the Python body,
+as it did before the binding read objects.  The Python
 functions below are unchanged; they are the fallback and the reference the
 native route is tested against (docs/design/native-greedy.md).
 """
@@ -31,7 +35,7 @@ from array import array
 from typing import Dict, List, Optional
 
 from ..config import OptimizerSpec, SaturationPolicy
-from ..core import Allocation, System
+from ..core import Allocation, Model, System
 
 
 class ServerEntry:
@@ -215,7 +219,65 @@ def _apply(servers, flat, offsets, chosen: List[int], granted: List[int]) -> Non
         server.set_allocation(alloc)
 
 
+def _solve_objects(system: System, spec: OptimizerSpec, binding) -> bool:
+    """The native solve with the candidates' fields read inside the binding
+    (csrc/greedy_py.h: greedy_solve_objects).  Python builds what is small:
+    the priority per server, the capacity per type, the type index per
+    accelerator and the units per (model, accelerator) pair that exists.
+    False when the binding, or a check here, leaves the decision to
+    _marshal; every server's allocation has been cleared by then."""
+    accelerators = system.accelerators
+    type_index: Dict[str, int] = {}
+    types: Dict[str, int] = {}
+    for name, acc in accelerators.items():
+        types[name] = type_index.setdefault(acc.type, len(type_index))
+    capacity = [0] * len(type_index)
+    for t, count in system.capacity.items():
+        i = type_index.get(t)
+        if i is not None:
+            capacity[i] = count
+    units: Dict[str, Dict[str, int]] = {}
+    for name, model in system.models.items():
+        if type(model) is not Model:
+            return False
+        units[name] = {
+            a: model.get_num_instances(a) * accelerators[a].multiplicity
+            for a in model.num_instances if a in accelerators
+        }
+
+    priorities: Dict[str, int] = {}  # per service class
+    servers = list(system.servers.values())
+    priority = []
+    for server in servers:
+        server.remove_allocation()
+        prio = 0
+        if server.all_allocations:
+            class_name = server.service_class_name
+            prio = priorities.get(class_name)
+            if prio is None:
+                prio = priorities[class_name] = server.priority(system)
+        priority.append(prio)
+    try:
+        if sum(map(abs, capacity)) >= _MAX_CAPACITY:
+            return False
+        capacity_arr = array("q", capacity)
+    except (TypeError, OverflowError):
+        return False
+    solved = binding.greedy_solve_objects(
+        servers, priority, capacity_arr, types, units, Allocation,
+        bool(spec.delayed_best_effort),
+        _POLICY_CODE[SaturationPolicy.parse(spec.saturation_policy)],
+    )
+    if solved is None:
+        return False
+    chosen, granted, flat, offsets = solved
+    _apply(servers, flat, offsets, chosen, granted)
+    return True
+
+
 def _solve_native(system: System, spec: OptimizerSpec, binding) -> bool:
+    if getattr(binding, "HAS_GREEDY_OBJECTS", False) and _solve_objects(system, spec, binding):
+        return True
     marshalled = _marshal(system)
     if marshalled is None:
         return False
