@@ -294,6 +294,44 @@ class QueueAnalyzer:
         erlang = np.cumsum(np.exp(i * math.log(x) - x - log_fact))  # [j - 1]: sum over i < j
         return float(np.dot(pi, erlang))
 
+    def ttft_quantile(self, request_rate: float, eps: float) -> float:
+        """The TTFT (ms) that an accepted arrival at ``request_rate`` (req/s)
+        exceeds with probability ``eps``: ``eps = 0.05`` is the p95 TTFT.
+
+        The inverse of ``wait_exceedance`` and the specification of every
+        native implementation (csrc/queue_core.h, "TTFT quantile").  With
+        ``p_wait = P(W > 0)``: nobody waits that often when ``p_wait <= eps``,
+        and t = 0; otherwise t is the root of ``P(W > t) = eps``, by
+        ``binary_search`` on ``[0, t_hi]`` with ``y(0) := p_wait``, where
+        ``t_hi = (J + sqrt(2 J l) + l) / mu_N``, ``J`` the queue length and
+        ``l = ln(2 / eps)``, holds ``P(W > t_hi) <= eps / 2`` (every
+        conditional wait is below Erlang(J, mu_N); Laurent-Massart).  The
+        result is ``wait_scale * t + prefill`` at the mean model's effective
+        concurrency.  Raises :class:`AnalyzerError` for an ``eps`` outside the
+        open (0, 1) and for a rate ``analyze`` rejects."""
+        if not 0.0 < eps < 1.0:  # also fails NaN
+            raise AnalyzerError(f"invalid TTFT tail probability {eps}")
+        if not 0.0 < request_rate <= self.rate_range.max:  # also fails NaN
+            raise AnalyzerError(f"invalid request rate {request_rate}")
+        lam = request_rate / 1000.0
+        m = self._solve(lam)
+        eff_conc = effective_concurrency(
+            m.avg_serv_time, self.service_parms, self.request_size, self.max_batch_size
+        )
+        prefill = self.service_parms.prefill.prefill_time(
+            self.request_size.avg_input_tokens, eff_conc
+        )
+        N, K = self.max_batch_size, self.model.K
+        p_wait = float(m.p[N:K].sum() / (1.0 - m.p[K]))
+        t = 0.0
+        if p_wait > eps:
+            J, mu_n, l = K - N, float(self.serv_rate[-1]), math.log(2.0 / eps)
+            t_hi = (J + math.sqrt(2.0 * J * l) + l) / mu_n
+            t, _ = binary_search(
+                0.0, t_hi, eps, lambda x: self._wait_exceedance(lam, x) if x > 0 else p_wait
+            )
+        return self._wait_scale * t + prefill
+
     def _eval_ttft_tail(self, target_ttft: float):
         """lam -> P(TTFT > target_ttft): the waiting time, stretched by the
         M/G/1 wait scale like the mean, has to fit what prefill leaves."""

@@ -47,7 +47,7 @@ class Allocation:
 
     __slots__ = (
         "accelerator", "num_replicas", "batch_size", "cost", "value",
-        "itl", "ttft", "rho", "max_arrv_rate_per_replica",
+        "itl", "ttft", "rho", "max_arrv_rate_per_replica", "_ttft_percentile",
     )
 
     def __init__(
@@ -70,6 +70,22 @@ class Allocation:
         self.ttft = ttft
         self.rho = rho
         self.max_arrv_rate_per_replica = max_arrv_rate_per_replica
+
+    @property
+    def ttft_percentile(self) -> float:
+        """Predicted TTFT (ms) at the sizing percentile (WVA_TTFT_PERCENTILE)
+        at this allocation's per-replica rate; 0.0 unless sized to a
+        percentile.  The slot behind it stays unset until somebody assigns:
+        the sizing cycle builds hundreds of allocations per step, and with the
+        knob unset a store per allocation is all this attribute would cost."""
+        try:
+            return self._ttft_percentile
+        except AttributeError:
+            return 0.0
+
+    @ttft_percentile.setter
+    def ttft_percentile(self, value: float) -> None:
+        self._ttft_percentile = value
 
     # -- accessors mirroring the reference API ------------------------------
     def set_value(self, value: float) -> None:
@@ -101,6 +117,8 @@ class Allocation:
             max_arrv_rate_per_replica=self.max_arrv_rate_per_replica,
         )
         a.value = self.value
+        if self.ttft_percentile != 0.0:
+            a.ttft_percentile = self.ttft_percentile
         return a
 
     def allocation_data(self) -> AllocationData:
@@ -212,9 +230,10 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
     from ..analyzer import configured_ttft_tail
 
     # WVA_TTFT_PERCENTILE: size to that percentile of TTFT, not to its mean
+    ttft_tail = configured_ttft_tail()
     target_perf = TargetPerf(
         target_ttft=target.ttft, target_itl=target.itl, target_tps=target.tps,
-        ttft_tail=configured_ttft_tail(),
+        ttft_tail=ttft_tail,
     )
     try:
         _, metrics, _ = qa.size(target_perf)
@@ -237,6 +256,8 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
     rate = total_rate / num_replicas
     try:
         metrics = qa.analyze(rate)
+        # sized to a percentile: predict that percentile too, not the mean alone
+        ttft_percentile = qa.ttft_quantile(rate, ttft_tail) if ttft_tail > 0 else 0.0
     except AnalyzerError:
         return None
 
@@ -250,6 +271,8 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
         rho=metrics.rho,
         max_arrv_rate_per_replica=rate_star / 1000.0,
     )
+    if ttft_tail > 0:
+        alloc.ttft_percentile = ttft_percentile
     alloc.set_value(alloc.cost)
     return alloc
 

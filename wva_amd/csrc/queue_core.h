@@ -687,6 +687,99 @@ WVA_HD double tail_sum_chunk(const TailSweep &w, int part, int parts) {
   return s0 + s1;
 }
 
+// ---------------------------------------------------------------------------
+// TTFT quantile: the inverse of the waiting-time tail.  Given a per-replica
+// rate rho (req/s) and a tail probability eps, the TTFT that an accepted
+// arrival exceeds with probability eps (eps = 0.05: the p95 TTFT).
+//
+// With lam = rho / 1000, st the mean-model evaluation at lam, prefill =
+// prefill_time(effective_concurrency(st.serv)), J = 10 N, mu_N = serv_rate(N)
+// and d = ln lam - ln mu_N:
+//   - p_wait = P(W > 0) = sum_{n=N..K-1} pi_n = pi_N expm1(J d) / expm1(d);
+//   - p_wait <= eps: nobody waits that often, t = 0;
+//   - otherwise t is the root of P(W > t) = eps, found by binary_search over t
+//     on [0, t_hi] with y(0) := p_wait and, for t > 0, y(t) the tail sum above
+//     (same window, same tail_probability);
+//   - q = wait_scale * t + prefill, in ms.
+// Lambda is fixed, so st, pi_N, d and the weights expm1((J - i) d) are
+// constants of the row: only the Poisson part of a term moves with t.
+//
+// Bracket.  Given the state, the wait is Erlang(j, mu_N) with j <= J, which is
+// stochastically below Erlang(J, mu_N), so P(W > t) <= P(Gamma(J, 1) > mu_N t).
+// Laurent-Massart: P(Gamma(J, 1) >= J + sqrt(2 J l) + l) <= e^-l.  With l =
+// ln(2 / eps) and t_hi = (J + sqrt(2 J l) + l) / mu_N this is P(W > t_hi) <=
+// eps / 2: the target lies strictly inside [0, t_hi] and is never within the
+// search's tolerance of its upper end.  (ln(2 / eps), not ln(1 / eps): p_wait
+// can be 1 - 1e-30 at large N, so nothing can be gained from pi.)
+//
+// The result row has two doubles, (valid, q): q = 0 is a legitimate value (a
+// decode-only row with nobody waiting).  (0, 0) for a row that fails
+// row_valid, an eps that is no finite number in the open (0, 1) (there is no
+// 100th percentile), or a rate that QueueAnalyzer.analyze rejects: NaN, +-inf,
+// <= 0, or above lam_max * 1000.
+// ---------------------------------------------------------------------------
+enum QuantileField { Q_VALID = 0, Q_TTFT, QUANTILE_FIELDS };
+
+// eps and the rate of a VALID row; ordered compares are false for NaN
+WVA_HD bool quantile_inputs_valid(const Parms &p, double rate, double eps) {
+  const double lam_max = serv_rate(p, p.max_batch) * (1.0 - kEpsilon);
+  return (eps > 0.0) & (eps < 1.0) & (rate > 0.0) & (rate <= lam_max * 1000.0);
+}
+
+// The constants of one row's search over t: uniform over everything that
+// shares the row.
+struct QuantileRow {
+  double lam;       // req/ms
+  double prefill;   // ms, at the mean evaluation's effective concurrency
+  double mu_n;      // serv_rate(N)
+  double d;         // ln lam - ln mu_N, < 0
+  double log_pi_n;  // ln pi_N
+  double p_wait;    // P(W > 0)
+  double t_hi;      // the bracket's upper end, ms
+  int J;
+};
+
+// st is the mean-model evaluation at lam and logp_n its log_p(N)
+WVA_HD QuantileRow quantile_row_of(const Parms &p, const Stats &st, double logp_n, double lam,
+                                   double eps) {
+  QuantileRow q;
+  q.lam = lam;
+  q.prefill = prefill_time(p, effective_concurrency(p, st.serv));
+  q.mu_n = serv_rate(p, p.max_batch);
+  q.d = log(lam) - log(q.mu_n);
+  q.J = p.max_batch * kMaxQueueToBatchRatio;
+  q.log_pi_n = logp_n - st.log_ref - log(st.accept_mass);
+  q.p_wait = exp(q.log_pi_n) * (expm1((double)q.J * q.d) / expm1(q.d));
+  const double l = log(2.0 / eps);
+  q.t_hi = ((double)q.J + sqrt(2.0 * (double)q.J * l) + l) / q.mu_n;
+  return q;
+}
+
+// tail_sweep_of for a given t > 0 instead of a TTFT target: the same scalars
+// and the same window rule
+WVA_HD TailSweep tail_sweep_at(const QuantileRow &q, double t) {
+  TailSweep w{false, 0.0, 0.0, 0.0, 0, 0, -1};
+  const double x = q.mu_n * t;
+  w.d = q.d;
+  w.a = log(x) + w.d;
+  w.log_c = q.log_pi_n - x;
+  w.J = q.J;
+  const double top = (double)(w.J - 1);
+  w.nu = q.lam * t;
+  const double c = floor(fmin(w.nu, top));
+  const double L = 37.54 + 2.0 * log((double)w.J);
+  const double h = 2.0 * L + 1.0 + sqrt(2.0 * L * c);
+  w.lo = (int)fmax(c - h, 0.0);
+  w.hi = (int)fmin(c + h, top);
+  w.c = (int)c;
+  return w;
+}
+
+// the closing arithmetic: from the searched t to the TTFT quantile
+WVA_HD double quantile_ttft(const Parms &p, const QuantileRow &q, double t) {
+  return p.wait_scale * t + q.prefill;
+}
+
 // Whether an evaluator offers exceedance(lam, target_ttft) = P(TTFT > target)
 // next to eval(lam); one that does not sizes to the mean TTFT alone, and the
 // callers route no row with ttft_tail > 0 to it.

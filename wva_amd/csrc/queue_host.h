@@ -135,6 +135,45 @@ inline void solve_one(const double *pr, double *out, double *cum, double scv = 1
   out[R_RHO] = vals.rho;
 }
 
+// TTFT quantile of one row (queue_core.h, "TTFT quantile"), sequentially: the
+// compact table, one mean evaluation at the row's rate, then binary_search
+// over t on the tail sum.  cum must hold N doubles and lf 10 * N log-factorials
+// (row_compact_length, quantile_tail_length); out gets (valid, q).
+inline void quantile_one(const double *pr, double rate, double eps, double *out, double *cum,
+                         const double *lf, double scv = 1.0) {
+  out[Q_VALID] = out[Q_TTFT] = 0.0;
+  if (!row_valid(pr, scv)) return;
+  const Parms p = parms_from_problem(pr, scv);
+  if (!quantile_inputs_valid(p, rate, eps)) return;
+  const HostCompactTable table(p, cum);
+  const double lam = rate / 1000.0;
+  const double logp_n = (double)p.max_batch * log(lam) - cum[p.max_batch - 1];
+  const QuantileRow q = quantile_row_of(p, table.eval(lam), logp_n, lam, eps);
+  double t = 0.0;
+  if (q.p_wait > eps) {
+    auto y = [&](double at) {
+      if (!(at > 0.0)) return q.p_wait;
+      const TailSweep w = tail_sweep_at(q, at);
+      return tail_probability(w, tail_sum(w, [lf](int i) { return lf[i]; }, 0, 1));
+    };
+    binary_search(0.0, q.t_hi, eps, y, &t);
+  }
+  out[Q_VALID] = 1.0;
+  out[Q_TTFT] = quantile_ttft(p, q, t);
+}
+
+// Length of the log-factorial table quantile_one needs for a batch: 10 * N of
+// its largest valid row.
+inline long long quantile_tail_length(const double *pr, long long rows) {
+  long long longest = 0;
+  for (long long i = 0; i < rows; ++i) {
+    const long long len =
+        (long long)row_compact_length(pr + i * PROBLEM_FIELDS) * kMaxQueueToBatchRatio;
+    if (len > longest) longest = len;
+  }
+  return longest;
+}
+
 // Scratch one thread needs for any row of a batch: the longest table, >= 1.
 template <typename Table>
 inline int batch_table_length(const double *pr, long long rows) {

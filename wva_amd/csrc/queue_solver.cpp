@@ -168,6 +168,37 @@ static torch::Tensor solve_allocations_tail_compact(
                                                  scv_data(ttft_tail, problems, "ttft_tail"));
 }
 
+// The TTFT quantile of every row at its own rate and eps (queue_core.h, "TTFT
+// quantile"), on the host: [B, 12] problems, float64 [B] rates (req/s per
+// replica) and eps, optional scv -> [B, 2] (valid, q).  CPU tensors only; on
+// the GPU the quantile kernel is reached through submit_quantile.
+static torch::Tensor ttft_quantiles(torch::Tensor problems, torch::Tensor rates,
+                                    torch::Tensor eps,
+                                    c10::optional<torch::Tensor> scv = c10::nullopt) {
+  check_problems(problems);
+  TORCH_CHECK(!problems.is_cuda(), "ttft_quantiles takes CPU tensors");
+  problems = problems.contiguous();
+  const int64_t B = problems.size(0);
+  auto out = torch::zeros({B, (int64_t)wva::QUANTILE_FIELDS}, problems.options());
+  const double *rate_ptr = scv_data(rates, problems, "rates");
+  const double *eps_ptr = scv_data(eps, problems, "eps");
+  const double *scv_ptr = scv_data(scv, problems);
+  if (B == 0) return out;
+  const double *pr = problems.data_ptr<double>();
+  double *res = out.data_ptr<double>();
+  const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
+  const std::vector<double> lf = wva::log_factorials(wva::quantile_tail_length(pr, B));
+  at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
+    std::vector<double> cum((size_t)table_len);
+    for (int64_t i = begin; i < end; ++i) {
+      wva::quantile_one(pr + i * wva::PROBLEM_FIELDS, rate_ptr[i], eps_ptr[i],
+                        res + i * wva::QUANTILE_FIELDS, cum.data(), lf.data(),
+                        scv_ptr ? scv_ptr[i] : 1.0);
+    }
+  });
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "wva_amd native batched queue solver (CPU + gfx950 HIP)";
   m.def("solve_allocations", &solve_allocations,
@@ -183,6 +214,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Poisson recurrence, no log-factorial table",
         pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
         pybind11::arg("ttft_tail") = pybind11::none());
+  m.def("ttft_quantiles", &ttft_quantiles,
+        "The TTFT each row exceeds with probability eps at its per-replica rate "
+        "(req/s), on the CPU: float64 [B, 2] of (valid, q in ms)",
+        pybind11::arg("problems"), pybind11::arg("rates"), pybind11::arg("eps"),
+        pybind11::arg("scv") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
   // greedy_solve, HAS_GREEDY
@@ -216,8 +252,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "checks and collect as submit",
         pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("tail"),
         pybind11::arg("scv") = pybind11::none());
+  m.def("submit_quantile", &wva::dispatch::submit_quantile,
+        "submit through the TTFT quantile kernel: rates (req/s per replica) and "
+        "eps are float64 [B] vectors; max_n is the largest max batch N the "
+        "launch reserves LDS for (10 * N doubles, up to 700); collect returns "
+        "[B, 2] of (valid, q in ms) for such a ticket",
+        pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("rates"),
+        pybind11::arg("eps"), pybind11::arg("scv") = pybind11::none());
   m.def("collect", &wva::dispatch::collect,
-        "Wait (GIL released) for a ticket and return its float64 [B, 6] results",
+        "Wait (GIL released) for a ticket and return its float64 results: [B, 6], "
+        "or [B, 2] for a submit_quantile ticket",
         pybind11::arg("ticket"));
   m.def("dispatch_pool_stats", &wva::dispatch::pool_stats,
         "(slots, slots in flight) of the dispatch pool");

@@ -65,7 +65,9 @@ namespace wva {
 // a seventh sizes rows to a TTFT percentile (the waiting-time tail kernel near
 // the end of the namespace: compact table plus a log-factorial table), and an
 // eighth does so without the second table, for N up to the compact limit (the
-// compact waiting-time tail kernel at the end of the namespace).
+// compact waiting-time tail kernel).  A ninth answers another question: the
+// TTFT quantile of a row at a given rate (the quantile kernel at the end of the
+// namespace).
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -971,6 +973,161 @@ extern "C" __global__ void __launch_bounds__(kTailThreads) wva_solve_kernel_tail
                                                              tail);
 }
 
+// ---------------------------------------------------------------------------
+// TTFT quantile kernel: the TTFT each row exceeds with probability eps at a
+// given per-replica rate (queue_core.h, "TTFT quantile").  The search runs
+// over t at a fixed lambda, so the mean model is evaluated once and
+// everything in a tail term that does not move with t is tabulated once.  One
+// workgroup of 256 threads per row, workgroup barriers only.
+//
+// LDS (doubles): tab[10 * max_n], totals[256], and of the 64 slack doubles
+// red[20] of the mean-model evaluator and slots[6] behind it.
+//
+// Phase A, the mean, once.  tab[0..N-1] is the compact cumulative table
+// (build_cum); one WgEval<256, LdsCompactTable>::eval(lam) leaves st, and with
+// log_p(N) the row's QuantileRow, on every thread.  p_wait <= eps ends the
+// row at (1, prefill); the decision is uniform over the workgroup.
+//
+// Phase B, the overlay.  The cumulative table is dead now, and tab is reused
+// for J = 10 N doubles
+//   logw[i] = ln(-expm1((J - i) d)) - ln i!,
+// ln i! by scan_table over ln i and the weight in one strided pass behind it.
+// A term of the tail sum is then -exp(i a(t) + logw[i] + log_c(t)): one fma
+// and one exp, where the tail kernel pays exp and expm1 and rebuilds the mean
+// sums for every candidate.
+//
+// Phase C, the search over t, speculative, one candidate per wave.  Each round
+// waves 0..2 evaluate the three nodes of the depth-2 midpoint tree of the
+// current bracket (heap_midpoint: the sequential iterates, bit for bit).  A
+// wave sums its own window alone: lane-strided over [lo, hi], so consecutive
+// lanes read consecutive logw entries, two exp chains, a __shfl_down
+// reduction, and lane 0 writes y to its slot.  The slots are double-buffered
+// by round parity, so a round costs one barrier: a wave that runs ahead writes
+// the other buffer, and the barrier of round r + 1 comes after every read of
+// round r.  Every thread then replays binary_search's walk on the three cached
+// values, two levels per round, with uniform control flow.  The opening round
+// evaluates y(t_hi) on wave 0; y(0) = p_wait is known.  Wave 3 helps with the
+// scans and the mean evaluation and otherwise only keeps the barriers.
+// ---------------------------------------------------------------------------
+constexpr int kQuantileThreads = 256;
+
+// y(t) by one wave: the windowed tail sum over the overlay table.  The same
+// value on every lane of the wave.
+__device__ inline double wave_quantile_tail(const QuantileRow &q, const double *logw, double t,
+                                            int lane) {
+  const TailSweep w = tail_sweep_at(q, t);
+  double s0 = 0.0, s1 = 0.0;
+  int i = w.lo + lane;
+  for (; i + 64 <= w.hi; i += 128) {
+    const int i2 = i + 64;
+    s0 += exp(fma((double)i, w.a, logw[i]) + w.log_c);
+    s1 += exp(fma((double)i2, w.a, logw[i2]) + w.log_c);
+  }
+  if (i <= w.hi) s0 += exp(fma((double)i, w.a, logw[i]) + w.log_c);
+  double sum = s0 + s1;
+  for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+  sum = __shfl(sum, 0, 64);
+  return tail_probability(w, -sum);  // the terms carry -expm1 > 0
+}
+
+__device__ void quantile_body(const double *__restrict__ prob, const double *__restrict__ scv,
+                              const double *__restrict__ rates,
+                              const double *__restrict__ eps_vec, double *__restrict__ out,
+                              int n_problems, int max_n) {
+  constexpr int THREADS = kQuantileThreads;
+  const int pid = blockIdx.x;
+  if (pid >= n_problems) return;
+  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
+  double *res = out + (size_t)pid * QUANTILE_FIELDS;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+
+  const double cs2 = row_scv(scv, pid);
+  const double rate = rates[pid];
+  const double eps = eps_vec[pid];
+  if (tid < QUANTILE_FIELDS) res[tid] = 0.0;
+  if (row_rejected<LdsCompactTable>(pr, cs2, max_n)) return;
+  const Parms p = parms_from_problem(pr, cs2);
+  if (!quantile_inputs_valid(p, rate, eps)) return;  // uniform: one row per workgroup
+
+  extern __shared__ double smem[];
+  double *tab = smem;  // cum[0..N-1], then logw[0..J-1]
+  double *totals = smem + max_n * kMaxQueueToBatchRatio;
+  double *red = totals + THREADS;
+  double *slots = red + 5 * (THREADS / 64);  // [2][3]
+
+  // Phase A
+  const LdsCompactTable table(p, tab);
+  build_cum<THREADS>(p, table.scan_length(), tab, totals);
+  const double lam = rate / 1000.0;
+  // before eval: behind its last barrier a thread reads red alone, so the
+  // overlay's scan may start without another barrier
+  const double logp_n = table.log_p(log(lam), p.max_batch);
+  const WgEval<THREADS, LdsCompactTable> ev{p, table, red};
+  const QuantileRow q = quantile_row_of(p, ev.eval(lam), logp_n, lam, eps);
+
+  double t = 0.0;
+  if (q.p_wait > eps) {
+    // Phase B
+    const int J = q.J;
+    scan_table<THREADS>(J, tab, totals, [](int i) { return i == 0 ? 0.0 : log((double)i); });
+    for (int i = tid; i < J; i += THREADS) {
+      tab[i] = log(-expm1((double)(J - i) * q.d)) - tab[i];
+    }
+    // (the opening round's barrier is not enough: wave 0 reads tab before it)
+    __syncthreads();
+
+    // Phase C
+    if (wave == 0) {
+      const double y = wave_quantile_tail(q, tab, q.t_hi, lane);
+      if (lane == 0) slots[0] = y;
+    }
+    __syncthreads();
+    bool increasing = false;
+    if (classify_bracket(0.0, q.t_hi, q.p_wait, slots[0], eps, &t, &increasing) == kBisect) {
+      double lo = 0.0, hi = q.t_hi;
+      int parity = 1, iters = 0;
+      bool done = false;
+      while (!done && iters < kMaxIterations) {
+        double *yb = slots + 3 * parity;
+        if (wave < 3) {
+          const double y = wave_quantile_tail(q, tab, heap_midpoint(lo, hi, wave + 1), lane);
+          if (lane == 0) yb[wave] = y;
+        }
+        __syncthreads();
+        parity ^= 1;
+        // binary_search's walk on the cached tree, two levels
+        int k = 1;
+        for (int level = 0; level < 2 && iters < kMaxIterations; ++level) {
+          t = 0.5 * (lo + hi);
+          const double ys = yb[k - 1];
+          ++iters;
+          if (within_tolerance(ys, eps, kTolerance)) {
+            done = true;
+            break;
+          }
+          if ((increasing && eps < ys) || (!increasing && eps > ys)) {
+            hi = t;
+            k = 2 * k;
+          } else {
+            lo = t;
+            k = 2 * k + 1;
+          }
+        }
+      }
+    }
+  }
+  if (tid < QUANTILE_FIELDS) res[tid] = (tid == Q_VALID) ? 1.0 : quantile_ttft(p, q, t);
+}
+
+extern "C" __global__ void __launch_bounds__(kQuantileThreads) wva_quantile_kernel(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    const double *__restrict__ rates, const double *__restrict__ eps_vec,
+    double *__restrict__ out, int n_problems, int max_n) {
+  quantile_body(prob, scv, rates, eps_vec, out, n_problems, max_n);
+}
+
 }  // namespace wva
 
 #include <cstdlib>
@@ -1087,5 +1244,25 @@ extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *s
   hipLaunchKernelGGL(wva::wva_solve_kernel_tail_compact, dim3(n_problems),
                      dim3(wva::kTailThreads), smem, (hipStream_t)stream, prob, scv, tail, out,
                      n_problems, max_n);
+  return (int)hipGetLastError();
+}
+
+// TTFT quantile launch: rates (req/s per replica) and eps are device vectors
+// of n_problems doubles, both required; max_n is the largest trunc(N) the
+// launch reserves LDS for, 10 * max_n doubles of table.  -1, and nothing
+// launched, without either vector or when 10 * max_n + 256 + 64 doubles exceed
+// 64 KiB (max_n beyond 787; callers route N above 700 elsewhere).
+extern "C" int wva_launch_quantile(const double *prob, const double *scv, const double *rates,
+                                   const double *eps, double *out, int n_problems, int max_n,
+                                   void *stream) {
+  constexpr int kPerState = wva::kMaxQueueToBatchRatio;
+  if (rates == nullptr || eps == nullptr || max_n < 1 || max_n > 64 * 1024 / 8 / kPerState) {
+    return -1;
+  }
+  const int table_len = max_n * kPerState;
+  if (!fits_lds(table_len, wva::kQuantileThreads)) return -1;
+  const size_t smem = (size_t)(table_len + wva::kQuantileThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_quantile_kernel, dim3(n_problems), dim3(wva::kQuantileThreads),
+                     smem, (hipStream_t)stream, prob, scv, rates, eps, out, n_problems, max_n);
   return (int)hipGetLastError();
 }

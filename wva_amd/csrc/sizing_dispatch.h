@@ -23,7 +23,10 @@
 // call.  A submit without one uploads the rows alone and launches with a
 // null vector: whatever an earlier submit left behind the rows of a reused
 // slot is never read.  A submit_tail or submit_tail_compact carries one more
-// vector, the rows' ttft_tail, behind that, in the same upload.
+// vector, the rows' ttft_tail, behind that, in the same upload.  A
+// submit_quantile carries two, the rows' eps and per-replica rates, and its
+// result rows are 2 doubles wide, not 6: the slot remembers the width for
+// collect.
 //
 // Buffers live in a pool of slots, each with pinned in/out, device in/out
 // and an event created with hipEventDisableTiming.  Slots are grow-only;
@@ -51,7 +54,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <string>
-#include <unordered_set>
+#include <unordered_map>
 #include <vector>
 
 #include "queue_core.h"
@@ -66,6 +69,9 @@ extern "C" int wva_launch_solve_tail(const double *prob, const double *scv, cons
 extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *scv,
                                              const double *tail, double *out, int n_problems,
                                              int max_n, void *stream);
+extern "C" int wva_launch_quantile(const double *prob, const double *scv, const double *rates,
+                                   const double *eps, double *out, int n_problems, int max_n,
+                                   void *stream);
 
 namespace wva {
 namespace dispatch {
@@ -98,7 +104,7 @@ struct DeviceGuard {
 enum class SlotState { kFree, kInFlight, kCollecting };
 
 struct Slot {
-  double *h_in = nullptr;   // pinned, cap_rows * (PROBLEM_FIELDS + 2): rows, scv, tail
+  double *h_in = nullptr;   // pinned, cap_rows * (PROBLEM_FIELDS + 3): rows, scv, tail, aux
   double *h_out = nullptr;  // pinned, cap_rows * RESULT_FIELDS
   double *d_in = nullptr;
   double *d_out = nullptr;
@@ -107,6 +113,7 @@ struct Slot {
   SlotState state = SlotState::kFree;
   int64_t ticket = 0;
   int64_t rows = 0;
+  int width = RESULT_FIELDS;  // doubles per result row of the launch in flight
 };
 
 struct Pool {
@@ -114,7 +121,7 @@ struct Pool {
   int device = -1;
   hipStream_t stream = nullptr;
   std::vector<Slot *> slots;  // slots never move or die once created
-  std::unordered_set<int64_t> empty_tickets;  // B == 0 submissions
+  std::unordered_map<int64_t, int> empty_tickets;  // B == 0 submissions: their width
   int64_t next_ticket = 1;
 };
 
@@ -135,9 +142,9 @@ inline void grow_slot(Slot &s, int64_t rows) {
   s.h_in = s.h_out = s.d_in = s.d_out = nullptr;
   s.cap_rows = 0;
   const int64_t cap = (rows + 255) / 256 * 256;
-  // two more doubles per row: the optional cs^2 and ttft_tail vectors
-  // behind the rows
-  const size_t in_bytes = (size_t)cap * (PROBLEM_FIELDS + 2) * sizeof(double);
+  // three more doubles per row: the optional cs^2, ttft_tail (or eps) and
+  // rate vectors behind the rows
+  const size_t in_bytes = (size_t)cap * (PROBLEM_FIELDS + 3) * sizeof(double);
   const size_t out_bytes = (size_t)cap * RESULT_FIELDS * sizeof(double);
   hip_check(hipHostMalloc((void **)&s.h_in, in_bytes, hipHostMallocDefault),
             "hipHostMalloc");
@@ -149,16 +156,19 @@ inline void grow_slot(Slot &s, int64_t rows) {
 }
 
 // any launcher of queue_solver_hip.hip; tail is null unless the submit
-// carries a ttft_tail vector, which only the tail kernel's launcher reads
-using Launcher = int (*)(const double *prob, const double *scv, const double *tail, double *out,
-                         int n_problems, int table_len, void *stream);
+// carries a ttft_tail (or eps) vector, which only the tail and quantile
+// kernels' launchers read, and aux unless it carries the quantile's rates
+using Launcher = int (*)(const double *prob, const double *scv, const double *tail,
+                         const double *aux, double *out, int n_problems, int table_len,
+                         void *stream);
 
 // The one submit.  `launch` gets table_len clamped to an int; when it answers
 // -1 (nothing was launched) the error reads not_fit_head, table_len,
 // not_fit_tail.
 inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t table_len,
                            const py::object &scv, const char *not_fit_head,
-                           const char *not_fit_tail, const py::object &tail = py::none()) {
+                           const char *not_fit_tail, const py::object &tail = py::none(),
+                           const py::object &aux = py::none(), int width = RESULT_FIELDS) {
   if (!py::isinstance<py::array_t<double>>(problems)) {
     throw py::type_error("problems must be a float64 array");
   }
@@ -173,13 +183,14 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
   if (B > INT_MAX) throw py::value_error("too many problems for one launch");
   const double *scv_src = scv_data(scv, B);
   const double *tail_src = row_vector_data(tail, B, "tail");
+  const double *aux_src = row_vector_data(aux, B, "rates");
 
   Pool &P = pool();
   std::lock_guard<std::mutex> lock(P.mu);
   if (B == 0) {
     // nothing to solve: no slot, no GPU call
     const int64_t ticket = P.next_ticket++;
-    P.empty_tickets.insert(ticket);
+    P.empty_tickets[ticket] = width;
     return ticket;
   }
   if (P.device < 0) hip_check(hipGetDevice(&P.device), "hipGetDevice");
@@ -213,14 +224,20 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
 
   const size_t row_doubles = (size_t)B * PROBLEM_FIELDS;
   const size_t scv_doubles = scv_src != nullptr ? (size_t)B : 0;
-  const size_t in_doubles = row_doubles + scv_doubles + (tail_src != nullptr ? (size_t)B : 0);
-  const size_t out_bytes = (size_t)B * RESULT_FIELDS * sizeof(double);
+  const size_t tail_doubles = tail_src != nullptr ? (size_t)B : 0;
+  const size_t in_doubles =
+      row_doubles + scv_doubles + tail_doubles + (aux_src != nullptr ? (size_t)B : 0);
+  const size_t out_bytes = (size_t)B * (size_t)width * sizeof(double);
   std::memcpy(slot->h_in, problems.data(), row_doubles * sizeof(double));
   if (scv_src != nullptr) {
     std::memcpy(slot->h_in + row_doubles, scv_src, (size_t)B * sizeof(double));
   }
   if (tail_src != nullptr) {
     std::memcpy(slot->h_in + row_doubles + scv_doubles, tail_src, (size_t)B * sizeof(double));
+  }
+  if (aux_src != nullptr) {
+    std::memcpy(slot->h_in + row_doubles + scv_doubles + tail_doubles, aux_src,
+                (size_t)B * sizeof(double));
   }
   hip_check(hipMemcpyAsync(slot->d_in, slot->h_in, in_doubles * sizeof(double),
                            hipMemcpyHostToDevice, P.stream),
@@ -229,8 +246,10 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
   const double *d_scv = scv_src != nullptr ? slot->d_in + row_doubles : nullptr;
   const double *d_tail =
       tail_src != nullptr ? slot->d_in + row_doubles + scv_doubles : nullptr;
+  const double *d_aux =
+      aux_src != nullptr ? slot->d_in + row_doubles + scv_doubles + tail_doubles : nullptr;
   const int status =
-      launch(slot->d_in, d_scv, d_tail, slot->d_out, (int)B, len, (void *)P.stream);
+      launch(slot->d_in, d_scv, d_tail, d_aux, slot->d_out, (int)B, len, (void *)P.stream);
   if (status != 0) {
     // nothing was launched; let the upload finish before the slot's pinned
     // buffer can be overwritten by the next submit
@@ -252,13 +271,15 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
   slot->state = SlotState::kInFlight;
   slot->ticket = P.next_ticket++;
   slot->rows = B;
+  slot->width = width;
   return slot->ticket;
 }
 
 // through the full-table kernels: max_k is the chain length 11 * N reserved
 inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::none()) {
   return submit_with(
-      [](const double *prob, const double *scv_vec, const double *, double *out, int n, int len,
+      [](const double *prob, const double *scv_vec, const double *, const double *, double *out,
+         int n, int len,
          void *stream) { return wva_launch_solve_scv(prob, scv_vec, out, n, len, stream); },
       problems, max_k, scv, "no kernel geometry holds a chain of length ",
       " in LDS (max_batch limit ~700); use the CPU path for these problems");
@@ -269,7 +290,8 @@ inline int64_t submit(py::array problems, int64_t max_k, py::object scv = py::no
 inline int64_t submit_compact(py::array problems, int64_t max_n,
                               py::object scv = py::none()) {
   return submit_with(
-      [](const double *prob, const double *scv_vec, const double *, double *out, int n, int len,
+      [](const double *prob, const double *scv_vec, const double *, const double *, double *out,
+         int n, int len,
          void *stream) { return wva_launch_solve_compact(prob, scv_vec, out, n, len, stream); },
       problems, max_n, scv, "the compact-table kernel cannot hold ",
       " states in LDS (max_batch limit ~7800); use the CPU path for these problems");
@@ -282,7 +304,11 @@ inline int64_t submit_tail(py::array problems, int64_t max_n, py::object tail,
                            py::object scv = py::none()) {
   if (tail.is_none()) throw py::type_error("tail must be a float64 array");
   return submit_with(
-      wva_launch_solve_tail, problems, max_n, scv, "the tail kernel cannot hold the tables of ",
+      [](const double *prob, const double *scv_vec, const double *tail_vec, const double *,
+         double *out, int n, int len, void *stream) {
+        return wva_launch_solve_tail(prob, scv_vec, tail_vec, out, n, len, stream);
+      },
+      problems, max_n, scv, "the tail kernel cannot hold the tables of ",
       " states in LDS (max_batch limit ~700); use the CPU path for these problems", tail);
 }
 
@@ -293,13 +319,37 @@ inline int64_t submit_tail_compact(py::array problems, int64_t max_n, py::object
                                    py::object scv = py::none()) {
   if (tail.is_none()) throw py::type_error("tail must be a float64 array");
   return submit_with(
-      wva_launch_solve_tail_compact, problems, max_n, scv,
+      [](const double *prob, const double *scv_vec, const double *tail_vec, const double *,
+         double *out, int n, int len, void *stream) {
+        return wva_launch_solve_tail_compact(prob, scv_vec, tail_vec, out, n, len, stream);
+      },
+      problems, max_n, scv,
       "the compact tail kernel cannot hold ",
       " states in LDS (max_batch limit ~7800); use the CPU path for these problems", tail);
 }
 
-inline std::vector<py::ssize_t> result_shape(int64_t rows) {
-  return {(py::ssize_t)rows, (py::ssize_t)RESULT_FIELDS};
+// through the TTFT quantile kernel (queue_core.h, "TTFT quantile"): rates is
+// the [B] vector of per-replica rates (req/s) and eps that of the tail
+// probabilities, both required; max_n is the largest max batch N the launch
+// reserves LDS for (10 * N doubles, up to ~700).  The ticket's results are
+// [B, 2]: (valid, q).
+inline int64_t submit_quantile(py::array problems, int64_t max_n, py::object rates,
+                               py::object eps, py::object scv = py::none()) {
+  if (rates.is_none() || eps.is_none()) {
+    throw py::type_error("rates and eps must be float64 arrays");
+  }
+  return submit_with(
+      [](const double *prob, const double *scv_vec, const double *eps_vec,
+         const double *rate_vec, double *out, int n, int len, void *stream) {
+        return wva_launch_quantile(prob, scv_vec, rate_vec, eps_vec, out, n, len, stream);
+      },
+      problems, max_n, scv, "the quantile kernel cannot hold the table of ",
+      " states in LDS (max_batch limit ~700); use the CPU path for these problems", eps, rates,
+      QUANTILE_FIELDS);
+}
+
+inline std::vector<py::ssize_t> result_shape(int64_t rows, int width = RESULT_FIELDS) {
+  return {(py::ssize_t)rows, (py::ssize_t)width};
 }
 
 inline py::array_t<double> collect(int64_t ticket) {
@@ -307,8 +357,11 @@ inline py::array_t<double> collect(int64_t ticket) {
   Slot *slot = nullptr;
   {
     std::lock_guard<std::mutex> lock(P.mu);
-    if (P.empty_tickets.erase(ticket)) {
-      return py::array_t<double>(result_shape(0));
+    const auto empty = P.empty_tickets.find(ticket);
+    if (empty != P.empty_tickets.end()) {
+      const int width = empty->second;
+      P.empty_tickets.erase(empty);
+      return py::array_t<double>(result_shape(0, width));
     }
     for (Slot *s : P.slots) {
       if (s->ticket == ticket && s->state != SlotState::kFree) {
@@ -325,14 +378,15 @@ inline py::array_t<double> collect(int64_t ticket) {
     slot->state = SlotState::kCollecting;  // a second collect now raises
   }
   const int64_t rows = slot->rows;
-  py::array_t<double> out(result_shape(rows));
+  const int width = slot->width;
+  py::array_t<double> out(result_shape(rows, width));
   double *dst = out.mutable_data();
   hipError_t err;
   {
     py::gil_scoped_release nogil;
     err = hipEventSynchronize(slot->done);
     if (err == hipSuccess) {
-      std::memcpy(dst, slot->h_out, (size_t)rows * RESULT_FIELDS * sizeof(double));
+      std::memcpy(dst, slot->h_out, (size_t)rows * (size_t)width * sizeof(double));
     }
     std::lock_guard<std::mutex> lock(P.mu);
     slot->state = SlotState::kFree;

@@ -85,8 +85,11 @@ def get_native():
 from .batched import (  # noqa: E402
     GPU_COMPACT_MAX_BATCH_LIMIT,
     GPU_MAX_BATCH_LIMIT,
+    Q_TTFT,
+    Q_VALID,
     BatchedAllocationSolver,
     solve_problems,
+    ttft_quantiles,
 )
 
 __all__ = [
@@ -96,6 +99,9 @@ __all__ = [
     "get_native_cpu",
     "BatchedAllocationSolver",
     "solve_problems",
+    "ttft_quantiles",
+    "Q_VALID",
+    "Q_TTFT",
     "GPU_MAX_BATCH_LIMIT",
     "GPU_COMPACT_MAX_BATCH_LIMIT",
 ]

@@ -125,6 +125,11 @@ PROBLEM_FIELDS = 12
 R_FEASIBLE, R_REPLICAS, R_RATE_STAR, R_ITL, R_TTFT, R_RHO = range(6)
 RESULT_FIELDS = 6
 
+# columns of a ttft_quantiles row: 1.0 for a row that got a value, and the
+# TTFT quantile in ms (0 is a legitimate one)
+Q_VALID, Q_TTFT = range(2)
+QUANTILE_FIELDS = 2
+
 # the GPU path keeps the cumulative table in LDS: N <= ~700
 GPU_MAX_BATCH_LIMIT = 700
 
@@ -691,6 +696,108 @@ def solve_problems(
     return _solve_problems_python(problems, scv=scv_arr)
 
 
+def _ttft_quantiles_python(problems, rates, eps, scv) -> np.ndarray:
+    """``ttft_quantiles`` row by row through ``QueueAnalyzer.ttft_quantile``,
+    the semantic reference; a rejected row is ``(0, 0)``."""
+    out = np.zeros((problems.shape[0], QUANTILE_FIELDS), dtype=np.float64)
+    valid = valid_rows(problems) & valid_scv(scv)
+    for i, row in enumerate(problems):
+        if not valid[i]:
+            continue
+        N = int(row[P_MAX_BATCH])
+        config = Configuration(
+            max_batch_size=N,
+            max_queue_size=N * MAX_QUEUE_TO_BATCH_RATIO,
+            service_parms=ServiceParms(
+                prefill=PrefillParms(gamma=row[P_GAMMA], delta=row[P_DELTA]),
+                decode=DecodeParms(alpha=row[P_ALPHA], beta=row[P_BETA]),
+            ),
+        )
+        size = RequestSize(avg_input_tokens=int(row[P_IN_TOKENS]),
+                           avg_output_tokens=int(row[P_OUT_TOKENS]))
+        try:
+            qa = QueueAnalyzer(config, size, scv=float(scv[i]))
+            out[i] = 1.0, qa.ttft_quantile(float(rates[i]), float(eps[i]))
+        except AnalyzerError:
+            continue
+    return out
+
+
+def ttft_quantiles(problems: np.ndarray, rates, eps, device: Optional[str] = None,
+                   scv=None) -> np.ndarray:
+    """The TTFT each row exceeds with probability ``eps`` at the per-replica
+    rate ``rates`` (req/s): [B, 12] problems -> [B, 2] of ``(Q_VALID, Q_TTFT)``
+    (csrc/queue_core.h, "TTFT quantile"; ``QueueAnalyzer.ttft_quantile`` is
+    the definition).  ``eps = 0.05`` asks for the p95 TTFT in ms.
+
+    ``rates``, ``eps`` and the optional ``scv`` follow ``_scv_vector``'s rules:
+    a scalar for the whole batch or a float64 ``[B]`` array.  A row gets
+    ``(0, 0)`` when it breaks the row contract, its ``scv`` is invalid, its
+    ``eps`` is no finite number in the open (0, 1), or its rate is NaN,
+    infinite, <= 0 or above the rate range's maximum; ``Q_VALID`` tells such a
+    row from a legitimate ``q = 0``.
+
+    device: as in ``solve_problems``.  On ``cuda`` the rows with N <=
+    GPU_MAX_BATCH_LIMIT (invalid rows ride along) run on the quantile kernel,
+    one launch, and rows with a larger N on the native CPU solver while that
+    launch runs.  Off the GPU: the torch-free binding, else the torch binding,
+    else the Python analyzer."""
+    from . import get_native, get_native_cpu, native_available, native_cpu_available
+
+    problems = np.ascontiguousarray(problems, dtype=np.float64)
+    if problems.ndim != 2 or problems.shape[1] != PROBLEM_FIELDS:
+        raise ValueError(f"problems must be [B, {PROBLEM_FIELDS}]")
+    n_rows = problems.shape[0]
+    rates = _scv_vector(rates, n_rows, "rates")
+    eps = _scv_vector(eps, n_rows, "eps")
+    scv_arr = None if scv is None else _scv_vector(scv, n_rows)
+    if n_rows == 0:
+        return np.zeros((0, QUANTILE_FIELDS), dtype=np.float64)
+
+    if device is not None and str(device).startswith("cuda"):
+        native = get_native()  # raises loudly if missing on a GPU box
+        limits = _valid_batch_limits(problems)
+        small = limits <= GPU_MAX_BATCH_LIMIT
+        if small.all():
+            with _on_device(device):
+                return native.collect(native.submit_quantile(
+                    problems, int(limits.max()), rates, eps, scv_arr))
+        out = np.empty((n_rows, QUANTILE_FIELDS), dtype=np.float64)
+
+        def part(mask):
+            return (np.ascontiguousarray(problems[mask]), np.ascontiguousarray(rates[mask]),
+                    np.ascontiguousarray(eps[mask]))
+
+        ticket = None
+        if small.any():
+            with _on_device(device):
+                ticket = native.submit_quantile(
+                    part(small)[0], int(limits[small].max()), *part(small)[1:],
+                    None if scv_arr is None else np.ascontiguousarray(scv_arr[small]))
+        try:
+            out[~small] = ttft_quantiles(*part(~small), device="cpu",
+                                         scv=None if scv_arr is None else scv_arr[~small])
+        finally:  # a launch already enqueued must not keep its slot for good
+            if ticket is not None:
+                out[small] = native.collect(ticket)
+        return out
+
+    if native_cpu_available():
+        return get_native_cpu().ttft_quantiles(problems, rates, eps, scv_arr)
+    if native_available():
+        import torch
+
+        return get_native().ttft_quantiles(
+            torch.from_numpy(problems), torch.from_numpy(rates), torch.from_numpy(eps),
+            None if scv_arr is None else torch.from_numpy(scv_arr),
+        ).numpy()
+    from . import warn_if_pure_python_fallback
+
+    warn_if_pure_python_fallback()
+    return _ttft_quantiles_python(
+        problems, rates, eps, np.ones(n_rows) if scv_arr is None else scv_arr)
+
+
 def _resolved_scv(scv_rows, global_scv: float) -> np.ndarray:
     """The rows' cs^2 with the "use the fleet value" sentinel (any negative
     value) replaced by ``global_scv``: the vector a solver may see."""
@@ -898,6 +1005,21 @@ class BatchedAllocationSolver:
             return SyncDispatch(self.device, dispatch_scv, tail), 1, True
         return SyncDispatch(self.device, ttft_tail=tail), self.chunks or 1, False
 
+    def _predict_percentiles(self, jobs, eps: float, global_scv: Optional[float]) -> None:
+        """``ttft_percentile`` of every allocation in ``jobs``: its row at the
+        per-replica rate ``create_allocation`` analyses, ``total_rate /
+        num_replicas``, in one ``ttft_quantiles`` call."""
+        problems = np.array([row for _, row, _ in jobs], dtype=np.float64)
+        rates = problems[:, P_TOTAL_RATE] / np.array([a.num_replicas for a, _, _ in jobs],
+                                                     dtype=np.float64)
+        scv = None
+        if global_scv is not None:
+            scv = _resolved_scv([s for _, _, s in jobs], global_scv)
+        solved = ttft_quantiles(problems, rates, eps, device=self.device, scv=scv)
+        for (alloc, _, _), (valid, q) in zip(jobs, solved.tolist()):
+            if valid == 1.0:
+                alloc.ttft_percentile = q
+
     def calculate(self, system: System) -> None:
         for g in system.accelerators.values():
             g.calculate()
@@ -942,6 +1064,11 @@ class BatchedAllocationSolver:
             and opt_spec.energy_cost_per_kwh > 0
         )
         servers = system.servers
+        # percentile sizing: every feasible allocation also gets its predicted
+        # TTFT at that percentile, from one ttft_quantiles call after the
+        # pipeline has drained: (allocation, row, its cs^2)
+        eps = dispatch.ttft_tail
+        quantile_jobs: List[Tuple[Allocation, Tuple[float, ...], float]] = []
 
         def build_rows(chunk_servers):
             """Build and submit the rows of one slice of servers; returns
@@ -1016,9 +1143,9 @@ class BatchedAllocationSolver:
             ticket = None
             if rows:
                 ticket = dispatch.submit(np.array(rows, dtype=np.float64), scv_rows)
-            return ticket, keys, zero_load
+            return ticket, keys, zero_load, (rows, scv_rows) if eps > 0 else None
 
-        def apply_results(ticket, keys, zero_load):
+        def apply_results(ticket, keys, zero_load, submitted=None):
             """Collect one slice and turn its results into Allocations."""
             if ticket is not None:
                 # plain floats beat numpy scalar access
@@ -1048,6 +1175,15 @@ class BatchedAllocationSolver:
                     alloc.value += energy_value_term(system, server, alloc)
                 server.all_allocations[acc_name] = alloc
 
+            if submitted is not None:
+                # a pass of its own, so that the loop above is what it is with
+                # the knob unset; (server, accelerator) is unique among the keys
+                rows, scv_rows = submitted
+                for i, (key, res) in enumerate(zip(keys, results_list)):
+                    if res[R_FEASIBLE] == 1.0:
+                        alloc = servers[key[0]].all_allocations[key[1]]
+                        quantile_jobs.append((alloc, rows[i], scv_rows[i] if scv_rows else -1.0))
+
             for server_name, accs in zero_load.items():
                 server = servers[server_name]
                 for acc_name, alloc in accs.items():
@@ -1075,6 +1211,8 @@ class BatchedAllocationSolver:
             if pending is not None:
                 last, pending = pending, None
                 apply_results(*last)
+            if quantile_jobs:
+                self._predict_percentiles(quantile_jobs, eps, dispatch.global_scv)
         finally:
             # an exception between submit and collect must not leave a
             # launch uncollected (its slot would stay busy for good)
