@@ -14,6 +14,16 @@ on a machine with an MI355X and the built extensions).
       worst oracle error over the bound of every implementation on the
       known-answer table of tests/test_ops_ttft_quantile.py.
 
+Every command but ``host`` takes a last argument ``large`` for the shapes of
+profiles/ttft_quantile_large_n.md: the compact quantile kernel against the
+compact tail kernel at B = 192, 4096 x N = 701, 1024, 7680, and both quantile
+kernels at N = 256, 700; ``large`` may be followed by the lower end of the
+rates' range as a fraction of the maximum (default 0.98).
+
+  python tools/ttft_quantile_bench.py host OUT.json [LOW]
+      the native host quantile solver alone on the large shapes: also runs on
+      an older build (from its directory, with this file's path).
+
 Shapes: B = 192, 4096 x N = 256, 700, the rows of tools/ttft_tail_bench.py
 (TTFT targets uniform in 300...3000 ms, which only the tail kernel reads),
 eps = 0.05 and per-replica rates uniform in 0.98...1 of the rate range's
@@ -35,10 +45,18 @@ sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 
 SHAPES = [(b, n) for b in (192, 4096) for n in (256, 700)]
 KERNELS = ("wva_quantile_kernel", "wva_solve_kernel_tail")
+LARGE_SHAPES = [(b, n) for b in (192, 4096) for n in (256, 700, 701, 1024, 7680)]
 WARMUP, REPS = 3, 30
 
 
-def rows(b, n):
+def large_kernels(n):
+    """The two kernels of a large shape, in launch order."""
+    if n <= 700:
+        return ("wva_quantile_kernel", "wva_quantile_kernel_compact")
+    return ("wva_quantile_kernel_compact", "wva_solve_kernel_tail_compact")
+
+
+def rows(b, n, low=0.98):
     rng = np.random.default_rng(7)
     p = np.zeros((b, 12))
     p[:, :7] = (4.137, 0.027, 5.2, 0.0011, 512, 128, n)
@@ -47,7 +65,7 @@ def rows(b, n):
     p[:, 11] = 1
     service = 5.2 + 0.0011 * 512 * n + 127 * (4.137 + 0.027 * n)
     rate_max = n / service * (1 - 0.001) * 1000.0  # req/s
-    rates = np.random.default_rng(13).uniform(0.98, 1.0, b) * rate_max
+    rates = np.random.default_rng(13).uniform(float(low), 1.0, b) * rate_max
     return p, rates, np.full(b, 0.05)
 
 
@@ -67,9 +85,66 @@ def launchers(native, p, n, rates, eps):
             "tail_kernel": lambda: native.collect(native.submit_tail(p, n, eps))}
 
 
-def roundtrip(out_path):
+def large_launchers(native, p, n, rates, eps):
+    compact = lambda: native.collect(native.submit_quantile_compact(p, n, rates, eps))
+    if n <= 700:
+        return {"quantile_kernel": lambda: native.collect(native.submit_quantile(p, n, rates, eps)),
+                "quantile_kernel_compact": compact}
+    return {"quantile_kernel_compact": compact,
+            "tail_kernel_compact": lambda: native.collect(native.submit_tail_compact(p, n, eps))}
+
+
+def searched(cpu, p, rates, ref):
+    # a row whose search did not run has q = prefill, what eps close to 1 gives
+    prefill = cpu.ttft_quantiles(p, rates, np.full(len(p), 1 - 1e-12))[:, 1]
+    return int((ref[:, 1] > prefill).sum())
+
+
+def roundtrip_large(out_path, low):
     from wva_amd import ops
 
+    native, cpu = ops.get_native(), ops.get_native_cpu()
+    out = []
+    for b, n in LARGE_SHAPES:
+        p, rates, eps = rows(b, n, low)
+        res = native.collect(native.submit_quantile_compact(p, n, rates, eps))
+        ref = cpu.ttft_quantiles(p, rates, eps)
+        ref_compact = cpu.ttft_quantiles_compact(p, rates, eps)
+        rel = lambda a, b_: float(np.abs(a[:, 1] / b_[:, 1] - 1).max())
+        rec = {"B": b, "N": n, "low": float(low), "valid": int(res[:, 0].sum()),
+               "valid_mismatch_vs_host": int((res[:, 0] != ref[:, 0]).sum()),
+               "searched": searched(cpu, p, rates, ref),
+               "q_max_rel_kernel_vs_host_compact": rel(res, ref_compact),
+               "q_max_rel_kernel_vs_host": rel(res, ref),
+               "q_max_rel_host_compact_vs_host": rel(ref_compact, ref)}
+        for name, fn in large_launchers(native, p, n, rates, eps).items():
+            rec[name] = timed(fn, reps=REPS if b * n < 4096 * 7680 else 10)
+        rec["host_quantile"] = timed(lambda: cpu.ttft_quantiles(p, rates, eps), reps=5)
+        rec["host_quantile_compact"] = timed(lambda: cpu.ttft_quantiles_compact(p, rates, eps),
+                                             reps=5)
+        out.append(rec)
+        print(json.dumps(rec), flush=True)
+    json.dump(out, open(out_path, "w"), indent=1)
+
+
+def host(out_path, low=0.98):
+    from wva_amd import ops
+
+    cpu = ops.get_native_cpu()
+    out = []
+    for b, n in LARGE_SHAPES:
+        p, rates, eps = rows(b, n, low)
+        out.append({"B": b, "N": n, "low": float(low),
+                    "host_quantile": timed(lambda: cpu.ttft_quantiles(p, rates, eps), reps=5)})
+        print(json.dumps(out[-1]), flush=True)
+    json.dump(out, open(out_path, "w"), indent=1)
+
+
+def roundtrip(out_path, which="small", low=0.98):
+    from wva_amd import ops
+
+    if which == "large":
+        return roundtrip_large(out_path, low)
     native, cpu = ops.get_native(), ops.get_native_cpu()
     out = []
     for b, n in SHAPES:
@@ -90,18 +165,19 @@ def roundtrip(out_path):
     json.dump(out, open(out_path, "w"), indent=1)
 
 
-def launches():
+def launches(which="small", low=0.98):
     from wva_amd import ops
 
     native = ops.get_native()
-    for b, n in SHAPES:
-        p, rates, eps = rows(b, n)
-        for fn in launchers(native, p, n, rates, eps).values():
+    for b, n in (LARGE_SHAPES if which == "large" else SHAPES):
+        p, rates, eps = rows(b, n, low)
+        pick = large_launchers if which == "large" else launchers
+        for fn in pick(native, p, n, rates, eps).values():
             for _ in range(WARMUP + REPS):
                 fn()
 
 
-def summarize(trace_path, out_path):
+def summarize(trace_path, out_path, which="small"):
     """Kernel-only times from the trace of ``launches``: its dispatches, in
     start order, are WARMUP + REPS of each of the two kernels for each shape
     (the trace does not tell N: the tables are in dynamic LDS).  The last REPS
@@ -109,9 +185,11 @@ def summarize(trace_path, out_path):
     runs = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"],
                    int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"]))
                   for r in csv.DictReader(open(trace_path))
-                  if r["Kernel_Name"].split(".")[0] in KERNELS)
+                  if r["Kernel_Name"].split(".")[0] in KERNELS + large_kernels(701))
     per = WARMUP + REPS
     plan = [(b, n, k) for b, n in SHAPES for k in KERNELS]
+    if which == "large":
+        plan = [(b, n, k) for b, n in LARGE_SHAPES for k in large_kernels(n)]
     assert len(runs) == per * len(plan), (len(runs), per * len(plan))
     out = []
     for i, (b, n, kernel) in enumerate(plan):
@@ -124,17 +202,22 @@ def summarize(trace_path, out_path):
     json.dump(out, open(out_path, "w"), indent=1)
 
 
-def parity(out_path):
+def parity(out_path, which="small"):
     import test_ops_ttft_quantile as T
     import torch
 
-    cases = [c for c in T.table() if c["tol"] is not None]
+    table, impls = T.table, T.IMPLS
+    if which == "large":
+        import test_ops_ttft_quantile_large_n as L
+
+        table, impls = L.table, L.IMPLS
+    cases = [c for c in table() if c["tol"] is not None]
     args = T.arrays(cases)
     want = np.array([c["t"] for c in cases])
     tol = np.array([c["tol"] for c in cases])
     prefill = np.array([c["prefill"] for c in cases])
     out = {}
-    for k, solve in T.IMPLS.items():
+    for k, solve in impls.items():
         if k.startswith("kernel") and not torch.cuda.is_available():
             continue
         t_got = (solve(*args)[:, 1] - prefill) / ((1 + args[3]) / 2)
@@ -148,4 +231,4 @@ def parity(out_path):
 
 if __name__ == "__main__":
     {"roundtrip": roundtrip, "launches": launches, "summarize": summarize,
-     "parity": parity}[sys.argv[1]](*sys.argv[2:])
+     "parity": parity, "host": host}[sys.argv[1]](*sys.argv[2:])

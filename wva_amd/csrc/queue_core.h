@@ -780,6 +780,89 @@ WVA_HD double quantile_ttft(const Parms &p, const QuantileRow &q, double t) {
   return p.wait_scale * t + q.prefill;
 }
 
+// ---------------------------------------------------------------------------
+// y(t) = P(W > t) of a QuantileRow without any table: the quantile search at
+// any N the compact table holds.  Window and scalars are tail_sweep_at's, the
+// window is cut into `parts` contiguous chunks as in tail_sum_chunk, and the
+// result is relative to the centre term in the same way (tail_centre_term).
+//
+// Lambda is fixed, so the geometric factor expm1((J - i) d) of a term is a
+// constant of the row and u_i = exp((J - i) d) a geometric sequence in i with
+// the ratio exp(-d) > 1 (quantile_growth, once per row).  A chunk forms u at
+// its first term with one exp and carries it along,
+//
+//   u_{i+2} = u_i exp(-2 d),   T_i = w_i (u_i - 1),
+//
+// next to the Poisson weight's stride-2 recurrence of tail_sum_chunk: two
+// multiply chains, one divide and no transcendental call per term, where
+// tail_sum_chunk pays an expm1.
+//
+// Underflow.  u grows along the chunk, so a first value that has underflowed
+// (or is denormal) would leave u = 0 at terms where the true u_i is not
+// negligible.  The chain is therefore taken only where (J - i0) |d| <=
+// kChainMaxExponent = 690: u_i0 >= e^-690 = 2e-300 is a normal number, every
+// later u_i is larger, and none exceeds u_{J-1} = e^d < 1 where it is read
+// (the value carried past the chunk's last term is at most e^{-2d} u_{J-1},
+// finite because a chunk that takes a step has J - i0 >= 2, that is 2 |d| <=
+// 690).  Any other chunk is tail_sum_chunk's, expm1 per term.
+//
+// Error.  Both chains take one step per two terms.  The longest chunk is the
+// host's and the kernel's alike, ceil(window / 64): the window has at most 2 h
+// + 1 = 6315 terms at J = 76800 (tail_sweep_at), so 99 terms and 50 steps.
+//   - The weight chain is tail_sum_chunk's: three roundings per step, 1.5 n
+//     2^-52 = 3.3e-14 over 99 terms, behind the first weight's 2e-10.
+//   - u: the first value carries exp's rounding and that of its argument,
+//     (J - i0) |d| 2^-53; a step multiplies by exp(-d)^2, a constant known to
+//     3 roundings, and rounds once: 4 2^-53 per step, 2.2e-14 over 50 steps.
+//   - u - 1 cancels.  Every valid rate has |d| >= -ln(1 - kEpsilon) = 1.0005e-3
+//     (lam <= mu_N (1 - kEpsilon)), and J - i >= 1 inside the window, so 1 -
+//     u_i >= 1 - e^-|d| >= 1e-3 and a relative error delta of u_i becomes
+//     delta u_i / (1 - u_i) <= delta / ((J - i) |d|) <= 1000 delta in the
+//     term.  For the drift and exp's rounding that is 1000 (2.2e-14 + 2.2e-16)
+//     = 2.3e-11.  The argument's share, (J - i0) |d| 2^-53 / ((J - i) |d|), is
+//     at most 100 2^-53 = 1.1e-14, since J - i0 <= 100 (J - i) over a chunk of
+//     99 terms.
+// Every term has the same sign, so the sum's relative error is at most the
+// worst term's, 2.3e-11: five orders inside the search's 1e-6 stop on y, and
+// below the first weight's own 2e-10.
+// ---------------------------------------------------------------------------
+constexpr double kChainMaxExponent = 690.0;
+
+// exp(-d): the ratio of the u chain, a constant of the row
+WVA_HD double quantile_growth(const QuantileRow &q) { return exp(-q.d); }
+
+// Chunk `part` of `parts` of the window, relative to the centre term; growth
+// is quantile_growth of the row w was made for.  <= 0; 0 for an empty chunk.
+WVA_HD double quantile_sum_chunk(const TailSweep &w, double growth, int part, int parts) {
+  const int len = (w.hi - w.lo + parts) / parts;  // ceil(window / parts)
+  const int i0 = w.lo + part * len;
+  const int end = i0 + len - 1 < w.hi ? i0 + len - 1 : w.hi;
+  if (i0 > end) return 0.0;
+  const double reach = (double)(w.J - i0) * w.d;  // ln u_i0, < 0
+  if (reach < -kChainMaxExponent) return tail_sum_chunk(w, part, parts);
+  const double nu2 = w.nu * w.nu;
+  const double growth2 = growth * growth;
+  double wa = exp((double)(i0 - w.c) * w.a - (log_factorial(i0) - log_factorial(w.c)));
+  double wb = wa * w.nu / (double)(i0 + 1);
+  double ua = exp(reach);
+  double ub = ua * growth;
+  double s0 = 0.0, s1 = 0.0;
+  int i = i0;
+  for (; i + 1 <= end; i += 2) {
+    s0 += wa * (ua - 1.0);
+    s1 += wb * (ub - 1.0);
+    wa *= nu2 / ((double)(i + 1) * (double)(i + 2));
+    wb *= nu2 / ((double)(i + 2) * (double)(i + 3));
+    ua *= growth2;
+    ub *= growth2;
+  }
+  if (i <= end) s0 += wa * (ua - 1.0);
+  return s0 + s1;
+}
+
+// The chunks one wave's lanes take, and the host sums in sequence
+constexpr int kQuantileChunks = 64;
+
 // Whether an evaluator offers exceedance(lam, target_ttft) = P(TTFT > target)
 // next to eval(lam); one that does not sizes to the mean TTFT alone, and the
 // callers route no row with ttft_tail > 0 to it.

@@ -162,6 +162,38 @@ inline void quantile_one(const double *pr, double rate, double eps, double *out,
   out[Q_TTFT] = quantile_ttft(p, q, t);
 }
 
+// quantile_one without the log-factorial table: y(t) by queue_core.h's
+// quantile_sum_chunk, over the kQuantileChunks chunks a wave of the compact
+// quantile kernel takes one per lane, summed here in sequence.  The host
+// reference of that kernel, not a routing target; cum must hold N doubles.
+inline void quantile_one_compact(const double *pr, double rate, double eps, double *out,
+                                 double *cum, double scv = 1.0) {
+  out[Q_VALID] = out[Q_TTFT] = 0.0;
+  if (!row_valid(pr, scv)) return;
+  const Parms p = parms_from_problem(pr, scv);
+  if (!quantile_inputs_valid(p, rate, eps)) return;
+  const HostCompactTable table(p, cum);
+  const double lam = rate / 1000.0;
+  const double logp_n = (double)p.max_batch * log(lam) - cum[p.max_batch - 1];
+  const QuantileRow q = quantile_row_of(p, table.eval(lam), logp_n, lam, eps);
+  double t = 0.0;
+  if (q.p_wait > eps) {
+    const double growth = quantile_growth(q);
+    auto y = [&](double at) {
+      if (!(at > 0.0)) return q.p_wait;
+      const TailSweep w = tail_sweep_at(q, at);
+      double sum = 0.0;
+      for (int part = 0; part < kQuantileChunks; ++part) {
+        sum += quantile_sum_chunk(w, growth, part, kQuantileChunks);
+      }
+      return tail_probability(w, tail_centre_term(w) * sum);
+    };
+    binary_search(0.0, q.t_hi, eps, y, &t);
+  }
+  out[Q_VALID] = 1.0;
+  out[Q_TTFT] = quantile_ttft(p, q, t);
+}
+
 // Length of the log-factorial table quantile_one needs for a batch: 10 * N of
 // its largest valid row.
 inline long long quantile_tail_length(const double *pr, long long rows) {

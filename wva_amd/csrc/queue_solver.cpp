@@ -171,7 +171,10 @@ static torch::Tensor solve_allocations_tail_compact(
 // The TTFT quantile of every row at its own rate and eps (queue_core.h, "TTFT
 // quantile"), on the host: [B, 12] problems, float64 [B] rates (req/s per
 // replica) and eps, optional scv -> [B, 2] (valid, q).  CPU tensors only; on
-// the GPU the quantile kernel is reached through submit_quantile.
+// the GPU the quantile kernels are reached through submit_quantile and
+// submit_quantile_compact.  kCompact: quantile_one_compact, the table-free
+// host reference of the compact quantile kernel, instead of quantile_one.
+template <bool kCompact>
 static torch::Tensor ttft_quantiles(torch::Tensor problems, torch::Tensor rates,
                                     torch::Tensor eps,
                                     c10::optional<torch::Tensor> scv = c10::nullopt) {
@@ -187,13 +190,19 @@ static torch::Tensor ttft_quantiles(torch::Tensor problems, torch::Tensor rates,
   const double *pr = problems.data_ptr<double>();
   double *res = out.data_ptr<double>();
   const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
-  const std::vector<double> lf = wva::log_factorials(wva::quantile_tail_length(pr, B));
+  const std::vector<double> lf =
+      wva::log_factorials(kCompact ? 0 : wva::quantile_tail_length(pr, B));
   at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
     std::vector<double> cum((size_t)table_len);
     for (int64_t i = begin; i < end; ++i) {
-      wva::quantile_one(pr + i * wva::PROBLEM_FIELDS, rate_ptr[i], eps_ptr[i],
-                        res + i * wva::QUANTILE_FIELDS, cum.data(), lf.data(),
-                        scv_ptr ? scv_ptr[i] : 1.0);
+      const double *row = pr + i * wva::PROBLEM_FIELDS;
+      double *q = res + i * wva::QUANTILE_FIELDS;
+      const double cs2 = scv_ptr ? scv_ptr[i] : 1.0;
+      if constexpr (kCompact) {
+        wva::quantile_one_compact(row, rate_ptr[i], eps_ptr[i], q, cum.data(), cs2);
+      } else {
+        wva::quantile_one(row, rate_ptr[i], eps_ptr[i], q, cum.data(), lf.data(), cs2);
+      }
     }
   });
   return out;
@@ -214,9 +223,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Poisson recurrence, no log-factorial table",
         pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
         pybind11::arg("ttft_tail") = pybind11::none());
-  m.def("ttft_quantiles", &ttft_quantiles,
+  m.def("ttft_quantiles", &ttft_quantiles<false>,
         "The TTFT each row exceeds with probability eps at its per-replica rate "
         "(req/s), on the CPU: float64 [B, 2] of (valid, q in ms)",
+        pybind11::arg("problems"), pybind11::arg("rates"), pybind11::arg("eps"),
+        pybind11::arg("scv") = pybind11::none());
+  m.def("ttft_quantiles_compact", &ttft_quantiles<true>,
+        "ttft_quantiles without a log-factorial table: the host reference of the "
+        "compact quantile kernel",
         pybind11::arg("problems"), pybind11::arg("rates"), pybind11::arg("eps"),
         pybind11::arg("scv") = pybind11::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
@@ -259,9 +273,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "[B, 2] of (valid, q in ms) for such a ticket",
         pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("rates"),
         pybind11::arg("eps"), pybind11::arg("scv") = pybind11::none());
+  m.def("submit_quantile_compact", &wva::dispatch::submit_quantile_compact,
+        "submit_quantile through the compact TTFT quantile kernel, which keeps no "
+        "table of the tail sum: max_n is the largest max batch N the launch "
+        "reserves LDS for (N doubles, up to ~7800)",
+        pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("rates"),
+        pybind11::arg("eps"), pybind11::arg("scv") = pybind11::none());
   m.def("collect", &wva::dispatch::collect,
         "Wait (GIL released) for a ticket and return its float64 results: [B, 6], "
-        "or [B, 2] for a submit_quantile ticket",
+        "or [B, 2] for a submit_quantile or submit_quantile_compact ticket",
         pybind11::arg("ticket"));
   m.def("dispatch_pool_stats", &wva::dispatch::pool_stats,
         "(slots, slots in flight) of the dispatch pool");

@@ -59,7 +59,10 @@ static py::array_t<double> solve_allocations(
 
 // The TTFT quantile of every row at its own rate and eps (queue_core.h, "TTFT
 // quantile"): [B, 12] problems, float64 [B] rates (req/s per replica) and eps,
-// optional scv -> [B, 2] (valid, q).
+// optional scv -> [B, 2] (valid, q).  kCompact: quantile_one_compact, the
+// table-free host reference of the compact quantile kernel, instead of
+// quantile_one.
+template <bool kCompact>
 static py::array_t<double> ttft_quantiles(
     py::array_t<double, py::array::c_style | py::array::forcecast> problems, py::object rates,
     py::object eps, py::object scv) {
@@ -77,7 +80,8 @@ static py::array_t<double> ttft_quantiles(
   if (B == 0) return out;
 
   const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
-  const std::vector<double> lf = wva::log_factorials(wva::quantile_tail_length(pr, B));
+  const std::vector<double> lf =
+      wva::log_factorials(kCompact ? 0 : wva::quantile_tail_length(pr, B));
   {
     py::gil_scoped_release release;
 #pragma omp parallel
@@ -85,9 +89,14 @@ static py::array_t<double> ttft_quantiles(
       std::vector<double> cum((size_t)table_len);
 #pragma omp for schedule(dynamic, 8)
       for (ssize_t i = 0; i < B; ++i) {
-        wva::quantile_one(pr + i * wva::PROBLEM_FIELDS, rate_ptr[i], eps_ptr[i],
-                          res + i * wva::QUANTILE_FIELDS, cum.data(), lf.data(),
-                          scv_ptr ? scv_ptr[i] : 1.0);
+        const double *row = pr + i * wva::PROBLEM_FIELDS;
+        double *q = res + i * wva::QUANTILE_FIELDS;
+        const double cs2 = scv_ptr ? scv_ptr[i] : 1.0;
+        if constexpr (kCompact) {
+          wva::quantile_one_compact(row, rate_ptr[i], eps_ptr[i], q, cum.data(), cs2);
+        } else {
+          wva::quantile_one(row, rate_ptr[i], eps_ptr[i], q, cum.data(), lf.data(), cs2);
+        }
       }
     }
   }
@@ -109,9 +118,13 @@ PYBIND11_MODULE(_queue_native_cpu, m) {
         "tail kernel",
         py::arg("problems"), py::arg("scv") = py::none(),
         py::arg("ttft_tail") = py::none());
-  m.def("ttft_quantiles", &ttft_quantiles,
+  m.def("ttft_quantiles", &ttft_quantiles<false>,
         "The TTFT each row exceeds with probability eps at its per-replica rate "
         "(req/s): float64 [B, 2] of (valid, q in ms)",
+        py::arg("problems"), py::arg("rates"), py::arg("eps"), py::arg("scv") = py::none());
+  m.def("ttft_quantiles_compact", &ttft_quantiles<true>,
+        "ttft_quantiles without a log-factorial table: the host reference of the "
+        "compact quantile kernel",
         py::arg("problems"), py::arg("rates"), py::arg("eps"), py::arg("scv") = py::none());
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;

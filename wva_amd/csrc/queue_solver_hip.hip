@@ -67,7 +67,8 @@ namespace wva {
 // eighth does so without the second table, for N up to the compact limit (the
 // compact waiting-time tail kernel).  A ninth answers another question: the
 // TTFT quantile of a row at a given rate (the quantile kernel at the end of the
-// namespace).
+// namespace), and a tenth answers it without a table of the tail sum, for N up
+// to the compact limit (the compact quantile kernel behind it).
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -1030,6 +1031,46 @@ __device__ inline double wave_quantile_tail(const QuantileRow &q, const double *
   return tail_probability(w, -sum);  // the terms carry -expm1 > 0
 }
 
+// Term policies of quantile_body: how many doubles of table a launch reserves
+// for max_n, what is prepared once the row is known to search (phase B), and
+// y(t) by one wave.
+
+// the overlay table logw[10 * N] over the dead cumulative table
+struct OverlayTerms {
+  const double *logw;
+  static __device__ int table_doubles(int max_n) { return max_n * kMaxQueueToBatchRatio; }
+  __device__ OverlayTerms(const QuantileRow &q, double *tab, double *totals) : logw(tab) {
+    constexpr int THREADS = kQuantileThreads;
+    const int J = q.J;
+    scan_table<THREADS>(J, tab, totals, [](int i) { return i == 0 ? 0.0 : log((double)i); });
+    for (int i = (int)threadIdx.x; i < J; i += THREADS) {
+      tab[i] = log(-expm1((double)(J - i) * q.d)) - tab[i];
+    }
+    // (the opening round's barrier is not enough: wave 0 reads tab before it)
+    __syncthreads();
+  }
+  __device__ double tail(const QuantileRow &q, double t, int lane) const {
+    return wave_quantile_tail(q, logw, t, lane);
+  }
+};
+
+// no table (queue_core.h, quantile_sum_chunk): the row's exp(-d), and lane l
+// takes the window's l-th contiguous chunk in registers
+struct ChainTerms {
+  double growth;
+  static __device__ int table_doubles(int max_n) { return max_n; }
+  __device__ ChainTerms(const QuantileRow &q, double *, double *) : growth(quantile_growth(q)) {}
+  __device__ double tail(const QuantileRow &q, double t, int lane) const {
+    const TailSweep w = tail_sweep_at(q, t);
+    double sum = quantile_sum_chunk(w, growth, lane, kQuantileChunks);
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    sum = __shfl(sum, 0, 64);
+    return tail_probability(w, tail_centre_term(w) * sum);
+  }
+};
+static_assert(kQuantileChunks == 64, "one chunk per lane of a wave");
+
+template <typename Terms>
 __device__ void quantile_body(const double *__restrict__ prob, const double *__restrict__ scv,
                               const double *__restrict__ rates,
                               const double *__restrict__ eps_vec, double *__restrict__ out,
@@ -1052,8 +1093,8 @@ __device__ void quantile_body(const double *__restrict__ prob, const double *__r
   if (!quantile_inputs_valid(p, rate, eps)) return;  // uniform: one row per workgroup
 
   extern __shared__ double smem[];
-  double *tab = smem;  // cum[0..N-1], then logw[0..J-1]
-  double *totals = smem + max_n * kMaxQueueToBatchRatio;
+  double *tab = smem;  // cum[0..N-1], then whatever Terms keeps
+  double *totals = smem + Terms::table_doubles(max_n);
   double *red = totals + THREADS;
   double *slots = red + 5 * (THREADS / 64);  // [2][3]
 
@@ -1070,17 +1111,11 @@ __device__ void quantile_body(const double *__restrict__ prob, const double *__r
   double t = 0.0;
   if (q.p_wait > eps) {
     // Phase B
-    const int J = q.J;
-    scan_table<THREADS>(J, tab, totals, [](int i) { return i == 0 ? 0.0 : log((double)i); });
-    for (int i = tid; i < J; i += THREADS) {
-      tab[i] = log(-expm1((double)(J - i) * q.d)) - tab[i];
-    }
-    // (the opening round's barrier is not enough: wave 0 reads tab before it)
-    __syncthreads();
+    const Terms terms(q, tab, totals);
 
     // Phase C
     if (wave == 0) {
-      const double y = wave_quantile_tail(q, tab, q.t_hi, lane);
+      const double y = terms.tail(q, q.t_hi, lane);
       if (lane == 0) slots[0] = y;
     }
     __syncthreads();
@@ -1092,7 +1127,7 @@ __device__ void quantile_body(const double *__restrict__ prob, const double *__r
       while (!done && iters < kMaxIterations) {
         double *yb = slots + 3 * parity;
         if (wave < 3) {
-          const double y = wave_quantile_tail(q, tab, heap_midpoint(lo, hi, wave + 1), lane);
+          const double y = terms.tail(q, heap_midpoint(lo, hi, wave + 1), lane);
           if (lane == 0) yb[wave] = y;
         }
         __syncthreads();
@@ -1125,7 +1160,34 @@ extern "C" __global__ void __launch_bounds__(kQuantileThreads) wva_quantile_kern
     const double *__restrict__ prob, const double *__restrict__ scv,
     const double *__restrict__ rates, const double *__restrict__ eps_vec,
     double *__restrict__ out, int n_problems, int max_n) {
-  quantile_body(prob, scv, rates, eps_vec, out, n_problems, max_n);
+  quantile_body<OverlayTerms>(prob, scv, rates, eps_vec, out, n_problems, max_n);
+}
+
+// ---------------------------------------------------------------------------
+// Compact TTFT quantile kernel: the same question at any N the compact table
+// holds (up to ~7800).  quantile_body over ChainTerms: the same row contract,
+// phase A and phase C as the quantile kernel above, and no phase B.
+//
+// LDS (doubles): cum[max_n], totals[256], and of the 64 slack doubles red[20]
+// and slots[6]: max_n + 256 + 64, the compact kernel's footprint.  After
+// phase A nothing but the slots is read from LDS.
+//
+// y(t) by one wave (ChainTerms::tail): tail_sweep_at gives the window, lane l
+// takes its l-th contiguous chunk of ceil(window / 64) terms (at most 99, near
+// saturation at N = 7680; a window shorter than 64 terms leaves the lanes
+// behind it an empty chunk).  A chunk costs two closed-form ln i! and two exp
+// for its first weight and its first u = exp((J - i) d), then per term a
+// multiply-divide for the Poisson weight and a multiply for u, both in the
+// stride-2 form, so two independent chains run in registers
+// (quantile_sum_chunk; a chunk whose u would start below e^-690 takes expm1
+// per term).  Then the __shfl_down reduction and the scaling by the centre
+// term, which every lane computes for itself.
+// ---------------------------------------------------------------------------
+extern "C" __global__ void __launch_bounds__(kQuantileThreads) wva_quantile_kernel_compact(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    const double *__restrict__ rates, const double *__restrict__ eps_vec,
+    double *__restrict__ out, int n_problems, int max_n) {
+  quantile_body<ChainTerms>(prob, scv, rates, eps_vec, out, n_problems, max_n);
 }
 
 }  // namespace wva
@@ -1264,5 +1326,23 @@ extern "C" int wva_launch_quantile(const double *prob, const double *scv, const 
   const size_t smem = (size_t)(table_len + wva::kQuantileThreads + 64) * sizeof(double);
   hipLaunchKernelGGL(wva::wva_quantile_kernel, dim3(n_problems), dim3(wva::kQuantileThreads),
                      smem, (hipStream_t)stream, prob, scv, rates, eps, out, n_problems, max_n);
+  return (int)hipGetLastError();
+}
+
+// Compact TTFT quantile launch: rates and eps as above, max_n the largest
+// trunc(N) the launch reserves LDS for, cum[max_n] alone.  -1, and nothing
+// launched, without either vector or when max_n + 256 + 64 doubles exceed
+// 64 KiB (max_n beyond 7872).
+extern "C" int wva_launch_quantile_compact(const double *prob, const double *scv,
+                                           const double *rates, const double *eps, double *out,
+                                           int n_problems, int max_n, void *stream) {
+  if (rates == nullptr || eps == nullptr || max_n < 1 ||
+      !fits_lds(max_n, wva::kQuantileThreads)) {
+    return -1;
+  }
+  const size_t smem = (size_t)(max_n + wva::kQuantileThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_quantile_kernel_compact, dim3(n_problems),
+                     dim3(wva::kQuantileThreads), smem, (hipStream_t)stream, prob, scv, rates,
+                     eps, out, n_problems, max_n);
   return (int)hipGetLastError();
 }

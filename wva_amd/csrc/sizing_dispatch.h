@@ -24,9 +24,9 @@
 // null vector: whatever an earlier submit left behind the rows of a reused
 // slot is never read.  A submit_tail or submit_tail_compact carries one more
 // vector, the rows' ttft_tail, behind that, in the same upload.  A
-// submit_quantile carries two, the rows' eps and per-replica rates, and its
-// result rows are 2 doubles wide, not 6: the slot remembers the width for
-// collect.
+// submit_quantile or submit_quantile_compact carries two, the rows' eps and
+// per-replica rates, and its result rows are 2 doubles wide, not 6: the slot
+// remembers the width for collect.
 //
 // Buffers live in a pool of slots, each with pinned in/out, device in/out
 // and an event created with hipEventDisableTiming.  Slots are grow-only;
@@ -72,6 +72,9 @@ extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *s
 extern "C" int wva_launch_quantile(const double *prob, const double *scv, const double *rates,
                                    const double *eps, double *out, int n_problems, int max_n,
                                    void *stream);
+extern "C" int wva_launch_quantile_compact(const double *prob, const double *scv,
+                                           const double *rates, const double *eps, double *out,
+                                           int n_problems, int max_n, void *stream);
 
 namespace wva {
 namespace dispatch {
@@ -345,6 +348,24 @@ inline int64_t submit_quantile(py::array problems, int64_t max_n, py::object rat
       },
       problems, max_n, scv, "the quantile kernel cannot hold the table of ",
       " states in LDS (max_batch limit ~700); use the CPU path for these problems", eps, rates,
+      QUANTILE_FIELDS);
+}
+
+// through the compact TTFT quantile kernel: the same rows, vectors and result
+// rows as submit_quantile, the tail sum without a table; max_n is the largest
+// max batch N the launch reserves LDS for (N doubles, up to ~7800)
+inline int64_t submit_quantile_compact(py::array problems, int64_t max_n, py::object rates,
+                                       py::object eps, py::object scv = py::none()) {
+  if (rates.is_none() || eps.is_none()) {
+    throw py::type_error("rates and eps must be float64 arrays");
+  }
+  return submit_with(
+      [](const double *prob, const double *scv_vec, const double *eps_vec,
+         const double *rate_vec, double *out, int n, int len, void *stream) {
+        return wva_launch_quantile_compact(prob, scv_vec, rate_vec, eps_vec, out, n, len, stream);
+      },
+      problems, max_n, scv, "the compact quantile kernel cannot hold ",
+      " states in LDS (max_batch limit ~7800); use the CPU path for these problems", eps, rates,
       QUANTILE_FIELDS);
 }
 

@@ -86,6 +86,16 @@ solve with a ``ttft_tail`` vector:
   ``submit_tail_compact``;
 - the same with ``large_n`` off (the default), or N > 7680: native CPU solver;
 - every other row: the route it takes without the vector.
+
+The TTFT each allocation exceeds at that percentile is predicted afterwards,
+by ``ttft_quantiles`` (one call per cycle).  Its routes on the GPU:
+
+- N <= 700: ``submit_quantile``;
+- 700 < N <= 7680, ``large_n`` on, not under ``WVA_GPU_GRAPH=1``:
+  ``submit_quantile_compact`` (the quantile search without a table of the tail
+  sum), one more launch, enqueued before anything is collected;
+- the same with ``large_n`` off (the default), or N > 7680: native CPU solver
+  while the launches run.
 """
 
 from __future__ import annotations
@@ -724,7 +734,7 @@ def _ttft_quantiles_python(problems, rates, eps, scv) -> np.ndarray:
 
 
 def ttft_quantiles(problems: np.ndarray, rates, eps, device: Optional[str] = None,
-                   scv=None) -> np.ndarray:
+                   scv=None, large_n: Optional[bool] = None) -> np.ndarray:
     """The TTFT each row exceeds with probability ``eps`` at the per-replica
     rate ``rates`` (req/s): [B, 12] problems -> [B, 2] of ``(Q_VALID, Q_TTFT)``
     (csrc/queue_core.h, "TTFT quantile"; ``QueueAnalyzer.ttft_quantile`` is
@@ -739,9 +749,17 @@ def ttft_quantiles(problems: np.ndarray, rates, eps, device: Optional[str] = Non
 
     device: as in ``solve_problems``.  On ``cuda`` the rows with N <=
     GPU_MAX_BATCH_LIMIT (invalid rows ride along) run on the quantile kernel,
-    one launch, and rows with a larger N on the native CPU solver while that
-    launch runs.  Off the GPU: the torch-free binding, else the torch binding,
-    else the Python analyzer."""
+    one launch.  Rows with a larger N run on the native CPU solver while that
+    launch runs, unless ``large_n`` is on: then those up to
+    GPU_COMPACT_MAX_BATCH_LIMIT run on the compact quantile kernel
+    (``submit_quantile_compact``, which keeps no table of the tail sum), one
+    more launch enqueued before anything is collected, and only rows beyond
+    that limit stay on the CPU.  Off the GPU: the torch-free binding, else the
+    torch binding, else the Python analyzer.
+
+    large_n: as in ``solve_problems``; ``None`` asks ``WVA_GPU_LARGE_N``.  No
+    effect off the GPU, on rows with N <= GPU_MAX_BATCH_LIMIT, or under
+    ``WVA_GPU_GRAPH=1``."""
     from . import get_native, get_native_cpu, native_available, native_cpu_available
 
     problems = np.ascontiguousarray(problems, dtype=np.float64)
@@ -768,18 +786,27 @@ def ttft_quantiles(problems: np.ndarray, rates, eps, device: Optional[str] = Non
             return (np.ascontiguousarray(problems[mask]), np.ascontiguousarray(rates[mask]),
                     np.ascontiguousarray(eps[mask]))
 
-        ticket = None
-        if small.any():
+        def launch(submit, mask):
             with _on_device(device):
-                ticket = native.submit_quantile(
-                    part(small)[0], int(limits[small].max()), *part(small)[1:],
-                    None if scv_arr is None else np.ascontiguousarray(scv_arr[small]))
+                return submit(part(mask)[0], int(limits[mask].max()), *part(mask)[1:],
+                              None if scv_arr is None else np.ascontiguousarray(scv_arr[mask]))
+
+        compact = ~small & (limits <= GPU_COMPACT_MAX_BATCH_LIMIT)
+        if not _large_n_requested(large_n):
+            compact[:] = False
+        host = ~small & ~compact
+        tickets = []
+        if small.any():
+            tickets.append((small, launch(native.submit_quantile, small)))
         try:
-            out[~small] = ttft_quantiles(*part(~small), device="cpu",
-                                         scv=None if scv_arr is None else scv_arr[~small])
+            if compact.any():
+                tickets.append((compact, launch(native.submit_quantile_compact, compact)))
+            if host.any():
+                out[host] = ttft_quantiles(*part(host), device="cpu",
+                                           scv=None if scv_arr is None else scv_arr[host])
         finally:  # a launch already enqueued must not keep its slot for good
-            if ticket is not None:
-                out[small] = native.collect(ticket)
+            for mask, ticket in tickets:
+                out[mask] = native.collect(ticket)
         return out
 
     if native_cpu_available():
@@ -1008,14 +1035,16 @@ class BatchedAllocationSolver:
     def _predict_percentiles(self, jobs, eps: float, global_scv: Optional[float]) -> None:
         """``ttft_percentile`` of every allocation in ``jobs``: its row at the
         per-replica rate ``create_allocation`` analyses, ``total_rate /
-        num_replicas``, in one ``ttft_quantiles`` call."""
+        num_replicas``, in one ``ttft_quantiles`` call (under the solver's
+        ``large_n``, as the sizing was)."""
         problems = np.array([row for _, row, _ in jobs], dtype=np.float64)
         rates = problems[:, P_TOTAL_RATE] / np.array([a.num_replicas for a, _, _ in jobs],
                                                      dtype=np.float64)
         scv = None
         if global_scv is not None:
             scv = _resolved_scv([s for _, _, s in jobs], global_scv)
-        solved = ttft_quantiles(problems, rates, eps, device=self.device, scv=scv)
+        solved = ttft_quantiles(problems, rates, eps, device=self.device, scv=scv,
+                                large_n=self.large_n)
         for (alloc, _, _), (valid, q) in zip(jobs, solved.tolist()):
             if valid == 1.0:
                 alloc.ttft_percentile = q
