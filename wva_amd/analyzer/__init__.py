@@ -26,6 +26,7 @@ from .queueanalyzer import (
     ServiceParms,
     TargetPerf,
     TargetRate,
+    configured_itl_tail,
     configured_ttft_tail,
     effective_concurrency,
     percentile_ttft_tail,
@@ -55,6 +56,7 @@ __all__ = [
     "TargetRate",
     "effective_concurrency",
     "configured_ttft_tail",
+    "configured_itl_tail",
     "percentile_ttft_tail",
     "MG1Corrector",
     "configured_scv",

@@ -121,21 +121,21 @@ class TargetPerf:
     # allowed probability that TTFT exceeds target_ttft (p95: 0.05); 0 sizes
     # to the mean TTFT; valid values are finite with 0 <= ttft_tail < 1
     ttft_tail: float = 0.0
+    # allowed fraction of tokens whose ITL exceeds target_itl (p95: 0.05); 0
+    # sizes to the mean ITL; valid values are finite with 0 <= itl_tail < 1
+    itl_tail: float = 0.0
 
     def check(self) -> None:
         if self.target_itl < 0 or self.target_ttft < 0 or self.target_tps < 0:
             raise AnalyzerError(f"invalid target data values {self}")
         if not 0.0 <= self.ttft_tail < 1.0:  # also fails NaN
             raise AnalyzerError(f"invalid TTFT tail probability {self}")
+        if not 0.0 <= self.itl_tail < 1.0:  # also fails NaN
+            raise AnalyzerError(f"invalid ITL tail fraction {self}")
 
 
-def configured_ttft_tail() -> float:
-    """The fleet's TTFT tail probability from ``WVA_TTFT_PERCENTILE`` (read
-    per call): ``95`` sizes to the p95 TTFT, ``ttft_tail = 0.05``.  Unset is
-    0.0: size to the mean TTFT.  So is a value that is no number in (0, 100)
-    (``0.95``, ``100``, ``p95``), with a warning, logged once per value: the
-    operator asked for a percentile and is not getting one."""
-    raw = os.environ.get("WVA_TTFT_PERCENTILE", "").strip()
+def _configured_tail(knob: str, what: str, rejected: set) -> float:
+    raw = os.environ.get(knob, "").strip()
     if not raw:
         return 0.0
     try:
@@ -144,16 +144,34 @@ def configured_ttft_tail() -> float:
             raise ValueError(raw)
         return percentile_ttft_tail(percentile)
     except ValueError:
-        if raw not in _rejected_percentiles:
-            _rejected_percentiles.add(raw)
+        if raw not in rejected:
+            rejected.add(raw)
             logging.getLogger("wva_amd.analyzer").warning(
-                "WVA_TTFT_PERCENTILE=%r is not a percentile in [1, 100) such as 95; "
-                "sizing to the MEAN TTFT", raw,
+                "%s=%r is not a percentile in [1, 100) such as 95; "
+                "sizing to the MEAN %s", knob, raw, what,
             )
         return 0.0
 
 
+def configured_ttft_tail() -> float:
+    """The fleet's TTFT tail probability from ``WVA_TTFT_PERCENTILE`` (read
+    per call): ``95`` sizes to the p95 TTFT, ``ttft_tail = 0.05``.  Unset is
+    0.0: size to the mean TTFT.  So is a value that is no number in (0, 100)
+    (``0.95``, ``100``, ``p95``), with a warning, logged once per value: the
+    operator asked for a percentile and is not getting one."""
+    return _configured_tail("WVA_TTFT_PERCENTILE", "TTFT", _rejected_percentiles)
+
+
+def configured_itl_tail() -> float:
+    """The fleet's ITL tail fraction from ``WVA_ITL_PERCENTILE`` (read per
+    call), with ``WVA_TTFT_PERCENTILE``'s semantics: ``95`` sizes to the p95
+    ITL, ``itl_tail = 0.05``; unset is 0.0, the mean ITL, and so is a rejected
+    value, with one warning per value."""
+    return _configured_tail("WVA_ITL_PERCENTILE", "ITL", _rejected_itl_percentiles)
+
+
 _rejected_percentiles: set = set()
+_rejected_itl_percentiles: set = set()
 
 
 def percentile_ttft_tail(percentile: float) -> float:
@@ -348,6 +366,29 @@ class QueueAnalyzer:
 
         return exceedance
 
+    def itl_exceedance(self, request_rate: float, target_itl: float) -> float:
+        """The fraction of tokens emitted at ``request_rate`` (req/s) whose
+        inter-token latency exceeds ``target_itl`` ms.
+
+        The direct definition, and the specification of every native
+        implementation (csrc/queue_core.h, "Occupancy tail"): a decode step
+        with ``b = min(n, N)`` requests in service takes ``decode_time(b)``, and
+        state n completes requests at rate mu(n), so tokens are emitted in
+        proportion to ``p[n] * mu(n)``:
+
+            y = sum_{n=1..K, decode_time(min(n,N)) > target} p[n] mu(n)
+                / sum_{n=1..K} p[n] mu(n)."""
+        return self._itl_exceedance(request_rate / 1000.0, target_itl)
+
+    def _itl_exceedance(self, lam_per_ms: float, target_itl: float) -> float:
+        m = self._solve(lam_per_ms)
+        N, K = self.max_batch_size, self.model.K
+        batch = np.minimum(np.arange(1, K + 1), N)
+        tokens = m.p[1:] * self.serv_rate[batch - 1]
+        decode = self.service_parms.decode
+        slow = decode.alpha + decode.beta * batch.astype(np.float64) > target_itl
+        return float(tokens[slow].sum() / tokens.sum())
+
     # -- public API ---------------------------------------------------------
     def analyze(self, request_rate: float) -> AnalysisMetrics:
         """Evaluate performance metrics at a given request rate (req/s)."""
@@ -421,7 +462,20 @@ class QueueAnalyzer:
                 )
 
         lambda_star_itl = lambda_max
-        if target_perf.target_itl > 0:
+        if target_perf.target_itl > 0 and target_perf.itl_tail > 0:
+            # percentile target: the share of tokens slower than target_itl
+            # against itl_tail
+            lambda_star_itl, ind = binary_search(
+                lambda_min, lambda_max, target_perf.itl_tail,
+                lambda lam: self._itl_exceedance(lam, target_perf.target_itl),
+            )
+            if ind == BelowRegion:
+                raise AnalyzerError(
+                    f"failed to calculate lambdaStarITL: the share of tokens above "
+                    f"{target_perf.target_itl} exceeds {target_perf.itl_tail} on the bounded "
+                    f"region {self.rate_range}"
+                )
+        elif target_perf.target_itl > 0:
             lambda_star_itl, ind = binary_search(
                 lambda_min, lambda_max, target_perf.target_itl, self._eval_itl
             )

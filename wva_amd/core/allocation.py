@@ -227,13 +227,14 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
     except AnalyzerError:
         return None
 
-    from ..analyzer import configured_ttft_tail
+    from ..analyzer import configured_itl_tail, configured_ttft_tail
 
-    # WVA_TTFT_PERCENTILE: size to that percentile of TTFT, not to its mean
+    # WVA_TTFT_PERCENTILE: size to that percentile of TTFT, not to its mean;
+    # WVA_ITL_PERCENTILE: the same for ITL
     ttft_tail = configured_ttft_tail()
     target_perf = TargetPerf(
         target_ttft=target.ttft, target_itl=target.itl, target_tps=target.tps,
-        ttft_tail=ttft_tail,
+        ttft_tail=ttft_tail, itl_tail=configured_itl_tail(),
     )
     try:
         _, metrics, _ = qa.size(target_perf)

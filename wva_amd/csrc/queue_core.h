@@ -84,6 +84,28 @@ constexpr int kMaxQueueToBatchRatio = 10;    // K = (1 + ratio) * N
 // solvers), and tail_sum_chunk, the Poisson recurrence without a table (the
 // compact tail kernel, N <= ~7800, and its host reference
 // solve_allocations_tail_compact).  They differ by rounding only.
+//
+// ITL percentile (per-row occupancy tail, "Occupancy tail" below):
+//   - a sizing row may carry itl_tail = eps, the allowed fraction of tokens
+//     whose ITL exceeds target_itl (p95 is eps = 0.05);
+//   - eps = 0 means "mean ITL": the search compares decode_time at the mean
+//     effective concurrency with the target, as it always did;
+//   - for eps > 0 the ITL search runs on y(lam), the token-weighted share of
+//     decode steps slower than target_itl, against the target value eps;
+//     binary_search and classify_bracket are the same: no batch size meeting
+//     the target (c = 0, y = 1) is infeasible, every batch size meeting it
+//     (c = N, y = 0) gives lam_max;
+//   - the TTFT search (mean or ttft_tail), the TPS back-off, the replica count
+//     and the final evaluation do not change, and R_ITL stays the predicted
+//     MEAN ITL at the final rate;
+//   - eps must be finite with 0 <= eps < 1; any other value gives the all-zero
+//     result row in every implementation;
+//   - a row with target_itl = 0 ignores a valid eps;
+//   - the layouts do not change: eps travels as a separate optional float64
+//     vector of length B (absent means 0 for every row), and composes with scv
+//     and ttft_tail on the same row.
+// No vector, or a vector of all 0, gives results bit-identical to the ones
+// without it on every path.
 enum ProblemField {
   P_ALPHA = 0,    // decode base (ms), >= 0
   P_BETA,         // decode slope (ms per batch unit), >= 0
@@ -130,10 +152,16 @@ constexpr int kMaxBatchLimit = 2147483647 / (1 + kMaxQueueToBatchRatio);
 // and nothing in it should make one load wait for another's compare.
 // scv is the row's service-time cs^2 (1.0 when the launch carries none):
 // finite and >= 0, so the -1 sentinel never passes.  tail_eps is the row's
-// ttft_tail (0 when the launch carries none): 0 <= eps < 1.
-WVA_HD bool row_valid(const double *pr, double scv = 1.0, double tail_eps = 0.0) {
+// ttft_tail (0 when the launch carries none): 0 <= eps < 1.  itl_eps is the
+// row's itl_tail under the same rule.  A target_itl that equals some
+// decode_time(m) to the last bit is outside the contract: the threshold count
+// below may then differ by one between two compilers' roundings of alpha +
+// beta * m.
+WVA_HD bool row_valid(const double *pr, double scv = 1.0, double tail_eps = 0.0,
+                      double itl_eps = 0.0) {
   bool ok = (scv >= 0.0) & (scv <= 1.7976931348623157e308);
   ok &= (tail_eps >= 0.0) & (tail_eps < 1.0);
+  ok &= (itl_eps >= 0.0) & (itl_eps < 1.0);
   for (int f = 0; f < PROBLEM_FIELDS; ++f) {
     ok &= fabs(pr[f]) <= 1.7976931348623157e308;  // fails NaN, +-inf
   }
@@ -877,6 +905,121 @@ constexpr bool has_exceedance(long) {
 }
 
 // ---------------------------------------------------------------------------
+// Occupancy tail: the share of tokens whose ITL exceeds a target, from the
+// same chain.
+//
+// A decode step with b = min(n, N) requests in service takes decode_time(b),
+// and every token it emits has that inter-token latency.  In state n the chain
+// completes requests at rate mu(n), so tokens are emitted in proportion to
+// p[n] mu(n), and the share of tokens slower than target_itl is
+//
+//   y(lam) = sum_{n=1..K, decode_time(min(n,N)) > target} p[n] mu(n)
+//            / sum_{n=1..K} p[n] mu(n).
+//
+// decode_time is non-decreasing in b, so the batch sizes that meet the target
+// are a prefix 1..c, c = itl_threshold_count.  Detailed balance, p[n] mu(n) =
+// lam p[n-1], turns both sums into sums of state probabilities, and the
+// denominator into the throughput lam (1 - p[K]):
+//
+//   y(lam) = 0                                   if c = N,
+//   y(lam) = sum_{j=c..K-1} pi_j,  pi_j = p[j] / (1 - p[K])   otherwise:
+//
+// the probability that an accepted arrival finds at least c requests in the
+// system (1 for c = 0).  The chain is stochastically increasing in lam, so y
+// is non-decreasing and binary_search runs on it over rate_bracket unchanged.
+//
+// Evaluation over the compact table, relative to e^m as in eval_model_compact:
+//   - the upper mass U = sum_{j=c..N} exp(log_p(j) - m) and the whole
+//     pre-batch mass A = sum_{j=0..N} exp(log_p(j) - m), term by term;
+//   - G, the states N+1..K-1 (not K), by geo_tail.  It never declines here:
+//     an evaluation happens only for 0 < c < N, so N >= 2, and on the bracket
+//     |d| >= -ln(1 - kEpsilon) = 1.0005e-3, so (10 N - 1) |d| >= 0.019 > 0.01;
+//   - y = (U + G) / (A + G).  U is summed directly, all terms positive: 1 -
+//     sum_{j<c} pi_j would cancel exactly where eps is small.
+// No Ni / Ninum moments, no effective concurrency.
+// ---------------------------------------------------------------------------
+
+// c = #{b in 1..N : decode_time(b) <= target_itl}: the last b that meets the
+// target, by bisection on the predicate every implementation shares.
+WVA_HD int itl_threshold_count(const Parms &p, double target_itl) {
+  int lo = 0, hi = p.max_batch;  // decode_time(lo) meets the target (or lo = 0)
+  while (lo < hi) {
+    const int mid = lo + (hi - lo + 1) / 2;
+    if (decode_time(p, (double)mid) <= target_itl) {
+      lo = mid;
+    } else {
+      hi = mid - 1;
+    }
+  }
+  return lo;
+}
+
+// The uniform scalars of one occupancy-tail evaluation: every thread that
+// shares it computes the same ones.
+struct OccupancySweep {
+  double loglam, m;  // log(lam) and the log reference, max(log_p(mode), 0)
+  double geo;        // G: the states N+1..K-1
+};
+
+WVA_HD OccupancySweep occupancy_sweep_of(const Parms &p, const double *cum, double log_mu_n,
+                                         double lam) {
+  const int N = p.max_batch;
+  const int K = N * (1 + kMaxQueueToBatchRatio);
+  OccupancySweep w;
+  w.loglam = log(lam);
+  w.m = log_p_compact(cum, N, log_mu_n, w.loglam, log_mode_state(p, K, lam));
+  if (w.m < 0.0) w.m = 0.0;
+  const GeoTail tail = geo_tail(log_p_compact(cum, N, log_mu_n, w.loglam, N + 1) - w.m,
+                                w.loglam - log_mu_n, N + 1, K - 1, K);
+  w.geo = tail.S;  // tail.used: N >= 2 and lam inside rate_bracket (above)
+  return w;
+}
+
+// Both mass sums over the states first, first + stride, ... <= N (first =
+// 0, stride = 1 is the whole sweep; a workgroup's threads take first = tid,
+// stride = THREADS and add their results).  Two independent exp chains per
+// pass, as in the mean model's sweep.
+WVA_HD void occupancy_sums(const OccupancySweep &w, const double *cum, int N, double log_mu_n,
+                           int c, int first, int stride, double *all, double *upper) {
+  double a0 = 0.0, a1 = 0.0, u0 = 0.0, u1 = 0.0;
+  int n = first;
+  for (; n + stride <= N; n += 2 * stride) {
+    const int n2 = n + stride;
+    const double e = exp(log_p_compact(cum, N, log_mu_n, w.loglam, n) - w.m);
+    const double e2 = exp(log_p_compact(cum, N, log_mu_n, w.loglam, n2) - w.m);
+    a0 += e;
+    a1 += e2;
+    u0 += n >= c ? e : 0.0;
+    u1 += n2 >= c ? e2 : 0.0;
+  }
+  if (n <= N) {
+    const double e = exp(log_p_compact(cum, N, log_mu_n, w.loglam, n) - w.m);
+    a0 += e;
+    u0 += n >= c ? e : 0.0;
+  }
+  *all = a0 + a1;
+  *upper = u0 + u1;
+}
+
+// y from the reduced sums; the clamp only trims rounding
+WVA_HD double occupancy_tail(const OccupancySweep &w, double all, double upper) {
+  return fmin(fmax((upper + w.geo) / (all + w.geo), 0.0), 1.0);
+}
+
+// Whether an evaluator offers itl_exceedance(lam, c) next to eval(lam), and
+// itl_eps(), the row's itl_tail; one that does not sizes to the mean ITL alone,
+// and the callers route no row with itl_tail > 0 to it.
+template <typename Ev>
+constexpr auto has_itl_exceedance(int)
+    -> decltype((void)((const Ev *)nullptr)->itl_exceedance(0.0, 0), true) {
+  return true;
+}
+template <typename Ev>
+constexpr bool has_itl_exceedance(long) {
+  return false;
+}
+
+// ---------------------------------------------------------------------------
 // Monotone bisection mirroring analyzer/search.py: boundary classification
 // -1 below / 0 within / +1 above, relative tolerance, 100 iterations.
 // ---------------------------------------------------------------------------
@@ -987,6 +1130,17 @@ WVA_HD bool search_targets(const double *pr, const Parms &p, const Ev &ev, doubl
   }
   *lam_itl = lam_max;
   if (pr[P_TARGET_ITL] > 0.0) {
+    // the ITL functional: the occupancy tail against eps for a row that
+    // carries one, the mean ITL against the target otherwise
+    if constexpr (has_itl_exceedance<Ev>(0)) {
+      if (ev.itl_eps() > 0.0) {
+        const int c = itl_threshold_count(p, pr[P_TARGET_ITL]);
+        if (c == 0) return false;               // y = 1 at every rate
+        if (c == p.max_batch) return true;      // y = 0 at every rate: lam_max
+        auto tail = [&](double lam) { return ev.itl_exceedance(lam, c); };
+        return binary_search(lam_min, lam_max, ev.itl_eps(), tail, lam_itl) >= 0;
+      }
+    }
     auto itl = [&](double lam) { return eval_itl_of(p, ev.eval(lam)); };
     if (binary_search(lam_min, lam_max, pr[P_TARGET_ITL], itl, lam_itl) < 0) return false;
   }

@@ -113,6 +113,40 @@ struct HostTailCompactTable : HostCompactTable {
   }
 };
 
+// HostTailCompactTable plus the occupancy tail (queue_core.h, "Occupancy
+// tail"): the evaluator of solve_allocations_ptile, the host reference of the
+// percentile kernel and the CPU route of rows that carry an itl_tail.  TTFT
+// side, mean model and table are the parent's, bit for bit.
+struct HostPtileTable : HostTailCompactTable {
+  double itl_tail;
+  HostPtileTable(const Parms &parms, double *table, double itl_eps)
+      : HostTailCompactTable(parms, table), itl_tail(itl_eps) {}
+  double itl_eps() const { return itl_tail; }
+  double itl_exceedance(double lam, int c) const {
+    const OccupancySweep w = occupancy_sweep_of(p, cum, log_mu_n, lam);
+    double all, upper;
+    occupancy_sums(w, cum, p.max_batch, log_mu_n, c, 0, 1, &all, &upper);
+    return occupancy_tail(w, all, upper);
+  }
+};
+
+// solve_one over HostPtileTable: itl_eps is the row's itl_tail (0: size to the
+// mean ITL).  cum must hold row_compact_length(pr) doubles.
+inline void solve_one_ptile(const double *pr, double *out, double *cum, double scv,
+                            double tail_eps, double itl_eps) {
+  for (int f = 0; f < RESULT_FIELDS; ++f) out[f] = 0.0;
+  if (!row_valid(pr, scv, tail_eps, itl_eps)) return;
+  const Parms p = parms_from_problem(pr, scv, tail_eps);
+  const HostPtileTable table(p, cum, itl_eps);
+  const RowValues vals = solve_row(pr, p, table);
+  out[R_FEASIBLE] = vals.feasible;
+  out[R_REPLICAS] = vals.replicas;
+  out[R_RATE_STAR] = vals.rate_star;
+  out[R_ITL] = vals.itl;
+  out[R_TTFT] = vals.ttft;
+  out[R_RHO] = vals.rho;
+}
+
 // Scalar solve of one problem (CPU path).  cum must hold Table::length(pr)
 // doubles; a row that breaks the contract of queue_core.h yields the
 // all-zero row and touches no table.  scv is the row's service-time cs^2

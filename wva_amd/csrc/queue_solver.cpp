@@ -168,6 +168,37 @@ static torch::Tensor solve_allocations_tail_compact(
                                                  scv_data(ttft_tail, problems, "ttft_tail"));
 }
 
+// solve_allocations_tail_compact with one more optional vector, the rows'
+// itl_tail (queue_core.h, "ITL percentile"): the host reference of the
+// percentile kernel, which is reached through submit_ptile, and the CPU route
+// of the rows that carry one.  CPU tensors only.
+static torch::Tensor solve_allocations_ptile(
+    torch::Tensor problems, c10::optional<torch::Tensor> scv = c10::nullopt,
+    c10::optional<torch::Tensor> ttft_tail = c10::nullopt,
+    c10::optional<torch::Tensor> itl_tail = c10::nullopt) {
+  check_problems(problems);
+  TORCH_CHECK(!problems.is_cuda(), "solve_allocations_ptile takes CPU tensors");
+  problems = problems.contiguous();
+  const double *scv_ptr = scv_data(scv, problems);
+  const double *tail_ptr = scv_data(ttft_tail, problems, "ttft_tail");
+  const double *itl_ptr = scv_data(itl_tail, problems, "itl_tail");
+  const int64_t B = problems.size(0);
+  auto out = torch::zeros({B, (int64_t)wva::RESULT_FIELDS}, problems.options());
+  if (B == 0) return out;
+  const double *pr = problems.data_ptr<double>();
+  double *res = out.data_ptr<double>();
+  const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
+  at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
+    std::vector<double> cum((size_t)table_len);
+    for (int64_t i = begin; i < end; ++i) {
+      wva::solve_one_ptile(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
+                           cum.data(), scv_ptr ? scv_ptr[i] : 1.0,
+                           tail_ptr ? tail_ptr[i] : 0.0, itl_ptr ? itl_ptr[i] : 0.0);
+    }
+  });
+  return out;
+}
+
 // The TTFT quantile of every row at its own rate and eps (queue_core.h, "TTFT
 // quantile"), on the host: [B, 12] problems, float64 [B] rates (req/s per
 // replica) and eps, optional scv -> [B, 2] (valid, q).  CPU tensors only; on
@@ -223,6 +254,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "Poisson recurrence, no log-factorial table",
         pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
         pybind11::arg("ttft_tail") = pybind11::none());
+  m.def("solve_allocations_ptile", &solve_allocations_ptile,
+        "solve_allocations_tail_compact with the rows' itl_tail: the ITL search on "
+        "the occupancy tail, the host reference of the percentile kernel",
+        pybind11::arg("problems"), pybind11::arg("scv") = pybind11::none(),
+        pybind11::arg("ttft_tail") = pybind11::none(),
+        pybind11::arg("itl_tail") = pybind11::none());
   m.def("ttft_quantiles", &ttft_quantiles<false>,
         "The TTFT each row exceeds with probability eps at its per-replica rate "
         "(req/s), on the CPU: float64 [B, 2] of (valid, q in ms)",
@@ -279,6 +316,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "reserves LDS for (N doubles, up to ~7800)",
         pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("rates"),
         pybind11::arg("eps"), pybind11::arg("scv") = pybind11::none());
+  m.def("submit_ptile", &wva::dispatch::submit_ptile,
+        "submit through the percentile kernel: rows whose ITL target is sized on "
+        "the occupancy tail, itl_tail the float64 [B] vector of their allowed "
+        "token share (required), ttft_tail the optional vector of the TTFT side; "
+        "max_n is the largest max batch N the launch reserves LDS for (N doubles, "
+        "up to 7872); split=True runs the measured alternative, both searches side "
+        "by side on one wave each; same slot pool, stream, checks and collect as submit",
+        pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("itl_tail"),
+        pybind11::arg("ttft_tail") = pybind11::none(), pybind11::arg("scv") = pybind11::none(),
+        pybind11::arg("split") = false);
   m.def("collect", &wva::dispatch::collect,
         "Wait (GIL released) for a ticket and return its float64 results: [B, 6], "
         "or [B, 2] for a submit_quantile or submit_quantile_compact ticket",

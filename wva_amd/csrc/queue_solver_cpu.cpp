@@ -57,6 +57,41 @@ static py::array_t<double> solve_allocations(
   return out;
 }
 
+// solve_allocations_tail_compact with one more optional vector, the rows'
+// itl_tail (queue_core.h, "ITL percentile"): the host reference of the
+// percentile kernel, and the CPU route of the rows that carry one.
+static py::array_t<double> solve_allocations_ptile(
+    py::array_t<double, py::array::c_style | py::array::forcecast> problems,
+    py::object scv, py::object ttft_tail, py::object itl_tail) {
+  auto buf = problems.request();
+  if (buf.ndim != 2 || buf.shape[1] != (ssize_t)wva::PROBLEM_FIELDS)
+    throw std::invalid_argument("problems must be [B, 12] float64");
+  const ssize_t B = buf.shape[0];
+  const double *scv_ptr = wva::scv_data(scv, B);
+  const double *tail_ptr = wva::row_vector_data(ttft_tail, B, "ttft_tail");
+  const double *itl_ptr = wva::row_vector_data(itl_tail, B, "itl_tail");
+  auto out = py::array_t<double>({B, (ssize_t)wva::RESULT_FIELDS});
+  const double *pr = (const double *)buf.ptr;
+  double *res = (double *)out.request().ptr;
+  if (B == 0) return out;
+
+  const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
+  {
+    py::gil_scoped_release release;
+#pragma omp parallel
+    {
+      std::vector<double> cum((size_t)table_len);
+#pragma omp for schedule(dynamic, 8)
+      for (ssize_t i = 0; i < B; ++i) {
+        wva::solve_one_ptile(pr + i * wva::PROBLEM_FIELDS, res + i * wva::RESULT_FIELDS,
+                             cum.data(), scv_ptr ? scv_ptr[i] : 1.0,
+                             tail_ptr ? tail_ptr[i] : 0.0, itl_ptr ? itl_ptr[i] : 0.0);
+      }
+    }
+  }
+  return out;
+}
+
 // The TTFT quantile of every row at its own rate and eps (queue_core.h, "TTFT
 // quantile"): [B, 12] problems, float64 [B] rates (req/s per replica) and eps,
 // optional scv -> [B, 2] (valid, q).  kCompact: quantile_one_compact, the
@@ -118,6 +153,11 @@ PYBIND11_MODULE(_queue_native_cpu, m) {
         "tail kernel",
         py::arg("problems"), py::arg("scv") = py::none(),
         py::arg("ttft_tail") = py::none());
+  m.def("solve_allocations_ptile", &solve_allocations_ptile,
+        "solve_allocations_tail_compact with the rows' itl_tail: the ITL search "
+        "on the occupancy tail, the host reference of the percentile kernel",
+        py::arg("problems"), py::arg("scv") = py::none(),
+        py::arg("ttft_tail") = py::none(), py::arg("itl_tail") = py::none());
   m.def("ttft_quantiles", &ttft_quantiles<false>,
         "The TTFT each row exceeds with probability eps at its per-replica rate "
         "(req/s): float64 [B, 2] of (valid, q in ms)",

@@ -68,7 +68,9 @@ namespace wva {
 // compact waiting-time tail kernel).  A ninth answers another question: the
 // TTFT quantile of a row at a given rate (the quantile kernel at the end of the
 // namespace), and a tenth answers it without a table of the tail sum, for N up
-// to the compact limit (the compact quantile kernel behind it).
+// to the compact limit (the compact quantile kernel behind it).  An eleventh
+// sizes a row's ITL target to a percentile as well (the percentile kernel
+// behind the compact waiting-time tail kernel, whose TTFT side it reuses).
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -975,6 +977,225 @@ extern "C" __global__ void __launch_bounds__(kTailThreads) wva_solve_kernel_tail
 }
 
 // ---------------------------------------------------------------------------
+// Percentile kernel: rows whose ITL target is sized to a percentile
+// (queue_core.h, "ITL percentile" and "Occupancy tail"), at any N the compact
+// table holds.  One workgroup of 256 threads per row, workgroup barriers only.
+// The occupancy tail needs no table besides cum[0..N-1], so there is one
+// kernel for N = 1 .. 7872 and no full-table variant.
+//
+// LDS (doubles): cum[max_n], totals[256], and of the 64 slack doubles
+//   red[20]       the mean-model evaluator's per-wave partials,
+//   tail_red[4]   the TTFT tail's,
+//   occ_red[16]   the occupancy tail's: [parity][wave][all, upper],
+// max_n + 256 + 64 in all, the compact kernels' footprint.
+//
+// The row's TTFT search is WgTailCompactEval's: the mean evaluator, or with
+// ttft_tail > 0 the table-free chunked recurrence.  Then the ITL search, on all
+// four waves as well (solve_row, in lockstep).  One evaluation of y(lam):
+//   - occupancy_sweep_of: log reference, geometric tail over N+1..K-1 and the
+//     sweep bound, scalar and uniform over the workgroup;
+//   - occupancy_sums with first = tid, stride = 256: thread tid takes states
+//     tid, tid + 256, ... <= N, two independent exp chains, two accumulators
+//     each for the whole and the upper mass; consecutive lanes read consecutive
+//     cum entries, conflict-free.  Two partials, where WgEval's sweep carries
+//     five and the moments' multiplies;
+//   - the __shfl_down reduction of both, lane 0 of each wave writes its pair,
+//     ONE barrier, and every thread adds the four pairs (broadcast reads).
+// occ_red is double-buffered by the evaluation's parity, which is what lets one
+// barrier do: a wave that runs ahead into evaluation k + 1 writes the other
+// buffer, and before it writes buffer k's again, in evaluation k + 2, it has
+// passed the barrier of k + 1, which every wave reaches only after its reads
+// of evaluation k.  occ_red is apart from red and tail_red, so the evaluators
+// of the TTFT search and of row_tail never meet it.
+// ---------------------------------------------------------------------------
+struct WgPtileEval {
+  static constexpr int WAVES = kTailThreads / 64;
+  const Parms &p;
+  WgTailCompactEval ttft;
+  double *occ_red;  // LDS, 2 * WAVES * 2
+  double eps;       // the row's itl_tail
+  mutable int parity;
+
+  __device__ Stats eval(double lam) const { return ttft.eval(lam); }
+  __device__ double exceedance(double lam, double target_ttft) const {
+    return ttft.exceedance(lam, target_ttft);
+  }
+  __device__ double itl_eps() const { return eps; }
+
+  __device__ double itl_exceedance(double lam, int c) const {
+    const LdsCompactTable &table = ttft.mean.table;
+    const OccupancySweep w = occupancy_sweep_of(p, table.cum, table.log_mu_n, lam);
+    double all, upper;
+    occupancy_sums(w, table.cum, table.N, table.log_mu_n, c, (int)threadIdx.x, kTailThreads,
+                   &all, &upper);
+    for (int off = 32; off > 0; off >>= 1) {
+      all += __shfl_down(all, off, 64);
+      upper += __shfl_down(upper, off, 64);
+    }
+    double *buf = occ_red + parity * (2 * WAVES);
+    parity ^= 1;
+    if ((threadIdx.x & 63) == 0) {
+      buf[(threadIdx.x >> 6) * 2 + 0] = all;
+      buf[(threadIdx.x >> 6) * 2 + 1] = upper;
+    }
+    __syncthreads();
+    all = upper = 0.0;
+    for (int wv = 0; wv < WAVES; ++wv) {
+      all += buf[wv * 2 + 0];
+      upper += buf[wv * 2 + 1];
+    }
+    return occupancy_tail(w, all, upper);
+  }
+};
+
+__device__ void solve_body_ptile(const double *__restrict__ prob, const double *__restrict__ scv,
+                                 const double *__restrict__ ttft_tail,
+                                 const double *__restrict__ itl_tail, double *__restrict__ out,
+                                 int n_problems, int max_n) {
+  constexpr int THREADS = kTailThreads;
+  const int pid = blockIdx.x;
+  if (pid >= n_problems) return;
+  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
+  double *res = out + (size_t)pid * RESULT_FIELDS;
+
+  const double cs2 = row_scv(scv, pid);
+  const double eps_ttft = ttft_tail != nullptr ? ttft_tail[pid] : 0.0;
+  const double eps_itl = itl_tail[pid];
+  zero_row(res);
+  // the row guard, before LDS is touched: both eps rules and trunc(N) <= max_n
+  if (!(row_valid(pr, cs2, eps_ttft, eps_itl) & LdsCompactTable::fits(pr, max_n))) return;
+  const Parms p = parms_from_problem(pr, cs2, eps_ttft);
+
+  extern __shared__ double smem[];
+  double *cum = smem;             // this row's N entries
+  double *totals = smem + max_n;  // THREADS chunk totals
+  double *red = totals + THREADS;
+  double *tail_red = red + 5 * WgPtileEval::WAVES;
+  double *occ_red = tail_red + WgPtileEval::WAVES;
+  static_assert(5 * WgPtileEval::WAVES + WgPtileEval::WAVES + 4 * WgPtileEval::WAVES <= 64,
+                "the partials outgrew the slack doubles");
+
+  const LdsCompactTable table(p, cum);
+  build_cum<THREADS>(p, table.scan_length(), cum, totals);
+
+  const WgPtileEval ev{p, {p, {p, table, red}, tail_red}, occ_red, eps_itl, 0};
+  store_row(res, solve_row(pr, p, ev));
+}
+
+// ---------------------------------------------------------------------------
+// The other search arrangement, kept for the measurement in
+// profiles/itl_tail.md and reached only through submit_ptile(..., split=True):
+// the TTFT and ITL searches side by side, as the dual kernel runs them.  Two
+// waves; wave 0 searches the TTFT target while wave 1 searches the ITL target,
+// each on one-wave, barrier-free evaluators (lane-strided sweeps, __shfl
+// reductions and broadcasts), so the waves diverge freely between the scan's
+// barrier and the one exchange barrier; wave 0 then finishes the row alone.
+// Same model, row guard and results up to rounding (the scan adds log_mu in
+// another order).  LDS: cum[max_n], totals[128], ex[4].  Measured on rows with
+// an ITL target alone (profiles/itl_tail.md): 0.5x to 0.75x the sequential
+// kernel's time at B = 4096 with N <= 1024, equal at B = 192, N = 256, and 1.2x
+// to 2.5x everywhere else (N = 7680 at either B, N >= 700 at B = 192).  No
+// route takes it yet: a pick by launch size, as wva_launch_solve_scv makes one
+// for the mean kernels, has not been measured on rows with both targets.
+// ---------------------------------------------------------------------------
+struct WavePtileEval {
+  const Parms &p;
+  WgEval<64, LdsCompactTable> mean;
+  double eps;  // the row's itl_tail
+
+  __device__ Stats eval(double lam) const { return mean.eval(lam); }
+  __device__ double itl_eps() const { return eps; }
+
+  __device__ double exceedance(double lam, double target_ttft) const {
+    const Stats st = mean.eval(lam);
+    const double logp_n = mean.table.log_p(log(lam), p.max_batch);
+    const TailSweep w = tail_sweep_of(p, st, logp_n, lam, target_ttft);
+    if (w.certain) return 1.0;  // uniform over the wave
+    double sum = tail_sum_chunk(w, (int)(threadIdx.x & 63), 64);
+    for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off, 64);
+    sum = __shfl(sum, 0, 64);
+    return tail_probability(w, tail_centre_term(w) * sum);
+  }
+
+  __device__ double itl_exceedance(double lam, int c) const {
+    const LdsCompactTable &table = mean.table;
+    const OccupancySweep w = occupancy_sweep_of(p, table.cum, table.log_mu_n, lam);
+    double all, upper;
+    occupancy_sums(w, table.cum, table.N, table.log_mu_n, c, (int)(threadIdx.x & 63), 64, &all,
+                   &upper);
+    for (int off = 32; off > 0; off >>= 1) {
+      all += __shfl_down(all, off, 64);
+      upper += __shfl_down(upper, off, 64);
+    }
+    return occupancy_tail(w, __shfl(all, 0, 64), __shfl(upper, 0, 64));
+  }
+};
+
+constexpr int kPtileSplitThreads = 128;
+
+__device__ void solve_body_ptile_split(const double *__restrict__ prob,
+                                       const double *__restrict__ scv,
+                                       const double *__restrict__ ttft_tail,
+                                       const double *__restrict__ itl_tail,
+                                       double *__restrict__ out, int n_problems, int max_n) {
+  constexpr int THREADS = kPtileSplitThreads;
+  const int pid = blockIdx.x;
+  if (pid >= n_problems) return;
+  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
+  double *res = out + (size_t)pid * RESULT_FIELDS;
+  const int wave = threadIdx.x >> 6;
+
+  const double cs2 = row_scv(scv, pid);
+  const double eps_ttft = ttft_tail != nullptr ? ttft_tail[pid] : 0.0;
+  const double eps_itl = itl_tail[pid];
+  zero_row(res);
+  if (!(row_valid(pr, cs2, eps_ttft, eps_itl) & LdsCompactTable::fits(pr, max_n))) return;
+  const Parms p = parms_from_problem(pr, cs2, eps_ttft);
+
+  extern __shared__ double smem[];
+  double *cum = smem;
+  double *totals = smem + max_n;
+  double *ex = totals + THREADS;  // lam_ttft, ok, lam_itl, ok
+
+  const LdsCompactTable table(p, cum);
+  build_cum<THREADS>(p, table.scan_length(), cum, totals);
+
+  double lam_min, lam_max;
+  rate_bracket(p, &lam_min, &lam_max);
+  const WavePtileEval ev{p, {p, table, nullptr}, eps_itl};
+
+  // search_targets over this wave's target alone: the other one is switched off
+  double targets[PROBLEM_FIELDS] = {};
+  targets[P_TARGET_TTFT] = wave == 0 ? pr[P_TARGET_TTFT] : 0.0;
+  targets[P_TARGET_ITL] = wave == 0 ? 0.0 : pr[P_TARGET_ITL];
+  double lam_ttft, lam_itl;
+  const bool ok = search_targets(targets, p, ev, lam_min, lam_max, &lam_ttft, &lam_itl);
+  if ((threadIdx.x & 63) == 0) {
+    ex[wave * 2 + 0] = wave == 0 ? lam_ttft : lam_itl;
+    ex[wave * 2 + 1] = ok ? 1.0 : 0.0;
+  }
+  __syncthreads();
+  if (ex[1] == 0.0 || ex[3] == 0.0) return;  // a target below the reachable range
+  if (wave == 1) return;                     // wave 0 finishes the row alone
+
+  store_row(res, row_tail(pr, p, ev, lam_max, ex[0], ex[2]));
+}
+
+extern "C" __global__ void __launch_bounds__(kPtileSplitThreads) wva_solve_kernel_ptile_split(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    const double *__restrict__ ttft_tail, const double *__restrict__ itl_tail,
+    double *__restrict__ out, int n_problems, int max_n) {
+  solve_body_ptile_split(prob, scv, ttft_tail, itl_tail, out, n_problems, max_n);
+}
+
+extern "C" __global__ void __launch_bounds__(kTailThreads) wva_solve_kernel_ptile(
+    const double *__restrict__ prob, const double *__restrict__ scv,
+    const double *__restrict__ ttft_tail, const double *__restrict__ itl_tail,
+    double *__restrict__ out, int n_problems, int max_n) {
+  solve_body_ptile(prob, scv, ttft_tail, itl_tail, out, n_problems, max_n);
+}
+
+// ---------------------------------------------------------------------------
 // TTFT quantile kernel: the TTFT each row exceeds with probability eps at a
 // given per-replica rate (queue_core.h, "TTFT quantile").  The search runs
 // over t at a fixed lambda, so the mean model is evaluated once and
@@ -1306,6 +1527,35 @@ extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *s
   hipLaunchKernelGGL(wva::wva_solve_kernel_tail_compact, dim3(n_problems),
                      dim3(wva::kTailThreads), smem, (hipStream_t)stream, prob, scv, tail, out,
                      n_problems, max_n);
+  return (int)hipGetLastError();
+}
+
+// Percentile launch: itl_tail is the device vector of the rows' itl_tail
+// (n_problems doubles, required), ttft_tail that of their ttft_tail or nullptr
+// (0 for every row), max_n the largest trunc(N) the launch reserves LDS for,
+// cum[max_n] alone.  -1, and nothing launched, without an itl_tail vector or
+// when max_n + 256 + 64 doubles exceed 64 KiB (max_n beyond 7872).
+extern "C" int wva_launch_solve_ptile(const double *prob, const double *scv,
+                                      const double *ttft_tail, const double *itl_tail,
+                                      double *out, int n_problems, int max_n, void *stream) {
+  if (itl_tail == nullptr || max_n < 1 || !fits_lds(max_n, wva::kTailThreads)) return -1;
+  const size_t smem = (size_t)(max_n + wva::kTailThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_solve_kernel_ptile, dim3(n_problems), dim3(wva::kTailThreads), smem,
+                     (hipStream_t)stream, prob, scv, ttft_tail, itl_tail, out, n_problems, max_n);
+  return (int)hipGetLastError();
+}
+
+// The same launch through the split arrangement (wva_solve_kernel_ptile_split):
+// same arguments, same refusals, 128 threads and max_n + 128 + 64 doubles.
+extern "C" int wva_launch_solve_ptile_split(const double *prob, const double *scv,
+                                            const double *ttft_tail, const double *itl_tail,
+                                            double *out, int n_problems, int max_n,
+                                            void *stream) {
+  if (itl_tail == nullptr || max_n < 1 || !fits_lds(max_n, wva::kTailThreads)) return -1;
+  const size_t smem = (size_t)(max_n + wva::kPtileSplitThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_solve_kernel_ptile_split, dim3(n_problems),
+                     dim3(wva::kPtileSplitThreads), smem, (hipStream_t)stream, prob, scv,
+                     ttft_tail, itl_tail, out, n_problems, max_n);
   return (int)hipGetLastError();
 }
 

@@ -26,7 +26,9 @@
 // vector, the rows' ttft_tail, behind that, in the same upload.  A
 // submit_quantile or submit_quantile_compact carries two, the rows' eps and
 // per-replica rates, and its result rows are 2 doubles wide, not 6: the slot
-// remembers the width for collect.
+// remembers the width for collect.  A submit_ptile carries the rows' itl_tail
+// in that last place, behind the optional cs^2 and ttft_tail: still one upload,
+// and nullptr for a vector that is absent.
 //
 // Buffers live in a pool of slots, each with pinned in/out, device in/out
 // and an event created with hipEventDisableTiming.  Slots are grow-only;
@@ -69,6 +71,13 @@ extern "C" int wva_launch_solve_tail(const double *prob, const double *scv, cons
 extern "C" int wva_launch_solve_tail_compact(const double *prob, const double *scv,
                                              const double *tail, double *out, int n_problems,
                                              int max_n, void *stream);
+extern "C" int wva_launch_solve_ptile(const double *prob, const double *scv,
+                                      const double *ttft_tail, const double *itl_tail,
+                                      double *out, int n_problems, int max_n, void *stream);
+extern "C" int wva_launch_solve_ptile_split(const double *prob, const double *scv,
+                                            const double *ttft_tail, const double *itl_tail,
+                                            double *out, int n_problems, int max_n,
+                                            void *stream);
 extern "C" int wva_launch_quantile(const double *prob, const double *scv, const double *rates,
                                    const double *eps, double *out, int n_problems, int max_n,
                                    void *stream);
@@ -160,7 +169,8 @@ inline void grow_slot(Slot &s, int64_t rows) {
 
 // any launcher of queue_solver_hip.hip; tail is null unless the submit
 // carries a ttft_tail (or eps) vector, which only the tail and quantile
-// kernels' launchers read, and aux unless it carries the quantile's rates
+// kernels' launchers read, and aux unless it carries the quantile's rates or
+// the percentile kernel's itl_tail
 using Launcher = int (*)(const double *prob, const double *scv, const double *tail,
                          const double *aux, double *out, int n_problems, int table_len,
                          void *stream);
@@ -171,7 +181,8 @@ using Launcher = int (*)(const double *prob, const double *scv, const double *ta
 inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t table_len,
                            const py::object &scv, const char *not_fit_head,
                            const char *not_fit_tail, const py::object &tail = py::none(),
-                           const py::object &aux = py::none(), int width = RESULT_FIELDS) {
+                           const py::object &aux = py::none(), int width = RESULT_FIELDS,
+                           const char *aux_name = "rates") {
   if (!py::isinstance<py::array_t<double>>(problems)) {
     throw py::type_error("problems must be a float64 array");
   }
@@ -186,7 +197,7 @@ inline int64_t submit_with(Launcher launch, const py::array &problems, int64_t t
   if (B > INT_MAX) throw py::value_error("too many problems for one launch");
   const double *scv_src = scv_data(scv, B);
   const double *tail_src = row_vector_data(tail, B, "tail");
-  const double *aux_src = row_vector_data(aux, B, "rates");
+  const double *aux_src = row_vector_data(aux, B, aux_name);
 
   Pool &P = pool();
   std::lock_guard<std::mutex> lock(P.mu);
@@ -329,6 +340,33 @@ inline int64_t submit_tail_compact(py::array problems, int64_t max_n, py::object
       problems, max_n, scv,
       "the compact tail kernel cannot hold ",
       " states in LDS (max_batch limit ~7800); use the CPU path for these problems", tail);
+}
+
+// through the percentile kernel: rows whose ITL target is sized on the
+// occupancy tail (queue_core.h, "ITL percentile").  itl_tail is the [B] vector
+// of their allowed token share (required), ttft_tail the optional one of the
+// TTFT side; max_n is the largest max batch N the launch reserves LDS for (N
+// doubles, up to 7872).  split runs the two searches side by side on one wave
+// each (wva_solve_kernel_ptile_split): the measured alternative, taken by no
+// route
+inline int64_t submit_ptile(py::array problems, int64_t max_n, py::object itl_tail,
+                            py::object ttft_tail = py::none(), py::object scv = py::none(),
+                            bool split = false) {
+  if (itl_tail.is_none()) throw py::type_error("itl_tail must be a float64 array");
+  const Launcher sequential = [](const double *prob, const double *scv_vec,
+                                 const double *tail_vec, const double *itl_vec, double *out,
+                                 int n, int len, void *stream) {
+    return wva_launch_solve_ptile(prob, scv_vec, tail_vec, itl_vec, out, n, len, stream);
+  };
+  const Launcher side_by_side = [](const double *prob, const double *scv_vec,
+                                   const double *tail_vec, const double *itl_vec, double *out,
+                                   int n, int len, void *stream) {
+    return wva_launch_solve_ptile_split(prob, scv_vec, tail_vec, itl_vec, out, n, len, stream);
+  };
+  return submit_with(
+      split ? side_by_side : sequential, problems, max_n, scv, "the percentile kernel cannot hold ",
+      " states in LDS (max_batch limit 7872); use the CPU path for these problems", ttft_tail,
+      itl_tail, RESULT_FIELDS, "itl_tail");
 }
 
 // through the TTFT quantile kernel (queue_core.h, "TTFT quantile"): rates is

@@ -96,6 +96,37 @@ by ``ttft_quantiles`` (one call per cycle).  Its routes on the GPU:
   sum), one more launch, enqueued before anything is collected;
 - the same with ``large_n`` off (the default), or N > 7680: native CPU solver
   while the launches run.
+
+ITL percentile (per-row occupancy tail; ``valid_tail`` here as well):
+
+- a sizing row may carry ``itl_tail = eps``, the allowed fraction of tokens
+  whose ITL exceeds ``target_itl`` (p95 is ``eps = 0.05``);
+- ``eps = 0`` means "mean ITL": the search compares the decode time at the
+  mean effective concurrency with the target, as it always did;
+- for ``eps > 0`` the ITL search runs on the token-weighted share of decode
+  steps slower than ``target_itl`` against the target value ``eps``;
+  ``QueueAnalyzer.itl_exceedance`` is its definition;
+- the TTFT search (mean or ``ttft_tail``), the TPS back-off, the replica count
+  and the final evaluation do not change, and ``R_ITL`` stays the predicted
+  *mean* ITL at the final rate;
+- ``eps`` must be finite with ``0 <= eps < 1``; any other value gives the
+  all-zero result row in every implementation;
+- a row with ``target_itl = 0`` ignores a valid ``eps``;
+- the layouts do not change: ``eps`` travels as a separate optional float64
+  vector of length B, and composes with ``scv`` and ``ttft_tail`` on a row.
+
+No vector, or a vector of all 0, gives results bit-identical to the ones
+without it on every path, through the code that ran before.  Routes of a GPU
+solve with an ``itl_tail`` vector (``_PtileTicket``):
+
+- eps > 0, target_itl > 0, N <= 700: ``submit_ptile``, one more ticket enqueued
+  before any is collected; the row's ``ttft_tail`` rides along;
+- the same with 700 < N <= 7680, ``large_n`` on, not under ``WVA_GPU_GRAPH=1``:
+  a second ``submit_ptile`` launch;
+- the same with ``large_n`` off, N > 7680, or under ``WVA_GPU_GRAPH=1``:
+  ``solve_allocations_ptile`` on the CPU while the launches run;
+- every other row: the route it takes without the vector; an invalid eps
+  gives the all-zero row.
 """
 
 from __future__ import annotations
@@ -117,6 +148,7 @@ from ..analyzer import (
     RequestSize,
     ServiceParms,
     TargetPerf,
+    configured_itl_tail,
     configured_ttft_tail,
     percentile_ttft_tail,
 )
@@ -459,24 +491,164 @@ class _TailTicket:
         return out
 
 
+def _ptile_rows(problems: np.ndarray, itl_arr: np.ndarray) -> np.ndarray:
+    """Mask of the rows whose ITL search runs on the occupancy tail: valid,
+    with a valid ``itl_tail`` > 0 and an ITL target."""
+    with np.errstate(invalid="ignore"):
+        return (valid_rows(problems) & valid_tail(itl_arr) & (itl_arr > 0)
+                & (problems[:, P_TARGET_ITL] > 0))
+
+
+def _masked(mask, problems, *vectors):
+    """The rows of ``mask`` and the same rows of each optional vector,
+    C-contiguous; a vector that is None stays None."""
+    return (np.ascontiguousarray(problems[mask]),
+            *(None if v is None else np.ascontiguousarray(v[mask]) for v in vectors))
+
+
+class _PtileTicket:
+    """One chunk split by ITL functional (an ``itl_tail`` vector), in flight.
+
+    - ``_ptile_rows`` with N <= GPU_MAX_BATCH_LIMIT went to
+      ``native.submit_ptile``, enqueued first, with their ``ttft_tail`` and cs^2;
+    - with ``large_n`` (already resolved by the caller), such rows with
+      GPU_MAX_BATCH_LIMIT < N <= GPU_COMPACT_MAX_BATCH_LIMIT went to a second
+      ``native.submit_ptile`` launch, which reserves LDS for their N alone;
+    - every other row went to ``submit_rest(rows, scv, ttft_tail)``: the route
+      it takes without the vector, bit for bit (a row whose ``itl_tail`` is
+      invalid rides along and is zeroed in the merge);
+    - the remaining percentile rows (N above the limit of the launches allowed;
+      all of them under ``WVA_GPU_GRAPH=1``) were solved by the native CPU
+      solver while the launches ran.
+
+    ``collect`` waits for every part and merges them back in row order."""
+
+    def __init__(self, native, device, problems, itl_arr, tail_arr, scv_arr, submit_rest,
+                 collect_rest, large_n=False):
+        self.native = native
+        self.n_rows = problems.shape[0]
+        self.collect_rest = collect_rest
+        self.bad = ~valid_tail(itl_arr)
+        wants = _ptile_rows(problems, itl_arr)
+        small = wants & (problems[:, P_MAX_BATCH] <= GPU_MAX_BATCH_LIMIT)
+        middle = wants & ~small & (problems[:, P_MAX_BATCH] <= GPU_COMPACT_MAX_BATCH_LIMIT)
+        if _graph_requested():
+            small = np.zeros_like(wants)
+        if not large_n or _graph_requested():
+            middle = np.zeros_like(wants)
+        self.rest, self.on_cpu = ~wants, wants & ~small & ~middle
+        self.tickets = []  # (row mask, native ticket)
+        self.rest_ticket = self.cpu_solved = None
+
+        def part(mask):
+            return _masked(mask, problems, scv_arr, tail_arr)
+
+        try:
+            for mask in (small, middle):
+                if mask.any():
+                    rows, scv, tail = part(mask)
+                    with _on_device(device):
+                        self.tickets.append((mask, native.submit_ptile(
+                            rows, int(rows[:, P_MAX_BATCH].max()),
+                            np.ascontiguousarray(itl_arr[mask]), tail, scv)))
+            if self.rest.any():
+                self.rest_ticket = submit_rest(*part(self.rest))
+            if self.on_cpu.any():
+                rows, scv, tail = part(self.on_cpu)
+                extra = {} if scv is None else {"scv": scv}
+                self.cpu_solved = solve_problems(
+                    rows, device="cpu", ttft_tail=tail,
+                    itl_tail=np.ascontiguousarray(itl_arr[self.on_cpu]), **extra)
+        except BaseException:
+            # a launch already enqueued must not keep its slot for good
+            try:
+                self.collect()
+            except Exception:
+                pass
+            raise
+
+    def collect(self) -> np.ndarray:
+        out = np.zeros((self.n_rows, RESULT_FIELDS), dtype=np.float64)
+        tickets, self.tickets = self.tickets, []
+        rest_ticket, self.rest_ticket = self.rest_ticket, None
+        error = None
+        try:  # every ticket is collected, whatever happens
+            if rest_ticket is not None:
+                out[self.rest] = self.collect_rest(rest_ticket)
+        except Exception as e:  # pragma: no cover - needs a failing GPU
+            error = e
+        for mask, ticket in tickets:
+            try:
+                out[mask] = self.native.collect(ticket)
+            except Exception as e:  # pragma: no cover - needs a failing GPU
+                error = error or e
+        if error is not None:
+            raise error
+        if self.cpu_solved is not None:
+            out[self.on_cpu] = self.cpu_solved
+        out[self.bad] = 0.0
+        return out
+
+
+def _solve_ptile_host(problems, device, scv_arr, tail_arr, itl_arr) -> np.ndarray:
+    """``solve_problems`` off the GPU with an ``itl_tail`` vector: the
+    ``_ptile_rows`` through ``solve_allocations_ptile`` of the torch-free
+    binding, else of the torch binding, else through the Python analyzer; every
+    other row by the call it gets without the vector."""
+    from . import get_native, get_native_cpu, native_available, native_cpu_available
+
+    out = np.zeros((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
+    wants = _ptile_rows(problems, itl_arr)
+
+    def part(mask):
+        return _masked(mask, problems, scv_arr, tail_arr)
+
+    if wants.any():
+        rows, scv, tail = part(wants)
+        itl = np.ascontiguousarray(itl_arr[wants])
+        if native_cpu_available():
+            out[wants] = get_native_cpu().solve_allocations_ptile(rows, scv, tail, itl)
+        elif native_available():
+            import torch
+
+            out[wants] = get_native().solve_allocations_ptile(
+                torch.from_numpy(rows), *(None if v is None else torch.from_numpy(v)
+                                          for v in (scv, tail, itl))).numpy()
+        else:
+            from . import warn_if_pure_python_fallback
+
+            warn_if_pure_python_fallback()
+            out[wants] = _solve_problems_python(
+                rows, 1.0 if scv is None else scv, 0.0 if tail is None else tail, itl)
+    if not wants.all():
+        rows, scv, tail = part(~wants)
+        extra = {} if scv is None else {"scv": scv}
+        out[~wants] = solve_problems(rows, device, ttft_tail=tail, **extra)
+    out[~valid_tail(itl_arr)] = 0.0
+    return out
+
+
 def _valid_batch_limits(problems: np.ndarray) -> np.ndarray:
     """Column N with the invalid rows' entries replaced by 1, so that they
     neither size a launch nor leave the GPU."""
     return np.where(valid_rows(problems), problems[:, P_MAX_BATCH], 1.0)
 
 
-def _solve_problems_python(problems: np.ndarray, scv=1.0, ttft_tail=0.0) -> np.ndarray:
+def _solve_problems_python(problems: np.ndarray, scv=1.0, ttft_tail=0.0,
+                           itl_tail=0.0) -> np.ndarray:
     """Reference-semantics scalar fallback via the Python analyzer.
 
     ``scv`` is the service-time cs^2 — a scalar for the whole batch or a
     per-row float64 array (mg1 auto mode derives one per server); a row
     whose cs^2 fails ``valid_scv`` yields the all-zero row.  ``ttft_tail``
     is the TTFT tail probability, a scalar or per-row likewise; a row whose
-    value fails ``valid_tail`` yields the all-zero row."""
+    value fails ``valid_tail`` yields the all-zero row.  ``itl_tail`` is the
+    ITL tail fraction under the same rules."""
     scv_arr = _scv_vector(scv, problems.shape[0])
     tail_arr = _scv_vector(ttft_tail, problems.shape[0], "ttft_tail")
+    itl_arr = _scv_vector(itl_tail, problems.shape[0], "itl_tail")
     out = np.zeros((problems.shape[0], RESULT_FIELDS), dtype=np.float64)
-    valid = valid_rows(problems) & valid_scv(scv_arr) & valid_tail(tail_arr)
+    valid = valid_rows(problems) & valid_scv(scv_arr) & valid_tail(tail_arr) & valid_tail(itl_arr)
     for i, row in enumerate(problems):
         if not valid[i]:
             continue  # all-zero row; also keeps int() off NaN and inf
@@ -504,6 +676,7 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0, ttft_tail=0.0) -> np.n
                     target_itl=row[P_TARGET_ITL],
                     target_tps=row[P_TARGET_TPS],
                     ttft_tail=float(tail_arr[i]),
+                    itl_tail=float(itl_arr[i]),
                 )
             )
             rate_star = metrics.throughput
@@ -525,7 +698,7 @@ def _solve_problems_python(problems: np.ndarray, scv=1.0, ttft_tail=0.0) -> np.n
 
 def solve_problems(
     problems: np.ndarray, device: Optional[str] = None, scv=None,
-    large_n: Optional[bool] = None, ttft_tail=None,
+    large_n: Optional[bool] = None, ttft_tail=None, itl_tail=None,
 ) -> np.ndarray:
     """Solve a [B, 12] problem matrix -> [B, 6] results.
 
@@ -559,6 +732,14 @@ def solve_problems(
     is on and to the native CPU solver otherwise (all tail rows under
     ``WVA_GPU_GRAPH=1``), and every other row takes the route it takes
     without the vector.
+
+    itl_tail: None, or the ITL tail fraction of the percentile sizing (module
+    docstring, "ITL percentile") — a scalar for the whole batch or a float64
+    ``[B]`` array.  None and all zeros are the mean ITL, on today's routes and
+    through today's code.  Otherwise the rows with ``eps > 0`` and an ITL
+    target run on the percentile kernel (``submit_ptile``) or, where the
+    module docstring's table says so, on ``solve_allocations_ptile`` on the
+    CPU; every other row takes the route it takes without the vector.
     """
     from . import get_native, native_available
 
@@ -571,6 +752,11 @@ def solve_problems(
         tail_arr = _scv_vector(ttft_tail, problems.shape[0], "ttft_tail")
         if not tail_arr.any():
             tail_arr = None  # all zeros: the mean TTFT, today's routes
+    itl_arr = None
+    if itl_tail is not None:
+        itl_arr = _scv_vector(itl_tail, problems.shape[0], "itl_tail")
+        if not itl_arr.any():
+            itl_arr = None  # all zeros: the mean ITL, today's routes
     if problems.shape[0] == 0:
         return np.zeros((0, RESULT_FIELDS), dtype=np.float64)
 
@@ -594,11 +780,14 @@ def solve_problems(
                 "M/G/1-corrected analyzer instead of the native kernel", scv,
             )
         return _solve_problems_python(
-            problems, scv=scv, ttft_tail=0.0 if tail_arr is None else tail_arr
+            problems, scv=scv, ttft_tail=0.0 if tail_arr is None else tail_arr,
+            itl_tail=0.0 if itl_arr is None else itl_arr,
         )
 
     want_gpu = device is not None and str(device).startswith("cuda")
-    if want_gpu and tail_arr is not None:
+    if itl_arr is not None and not want_gpu:
+        return _solve_ptile_host(problems, device, scv_arr, tail_arr, itl_arr)
+    if want_gpu and (tail_arr is not None or itl_arr is not None):
         native = get_native()  # raises loudly if missing on a GPU box
 
         def submit_rest(rows, rows_scv):
@@ -618,8 +807,24 @@ def solve_problems(
         def collect_rest(ticket):
             return ticket[1] if ticket[0] is None else native.collect(ticket[0])
 
-        split = _TailTicket(native, device, problems, tail_arr, scv_arr, submit_rest,
-                            collect_rest, large_n=_large_n_requested(large_n))
+        if itl_arr is None:
+            split = _TailTicket(native, device, problems, tail_arr, scv_arr, submit_rest,
+                                collect_rest, large_n=_large_n_requested(large_n))
+            return split.collect()
+
+        def submit_other(rows, rows_scv, rows_tail):
+            """The rows the percentile kernel does not take: a ``_TailTicket``
+            where some carry a ``ttft_tail``, ``submit_rest`` otherwise."""
+            if rows_tail is None or not rows_tail.any():
+                return submit_rest(rows, rows_scv)
+            return _TailTicket(native, device, rows, rows_tail, rows_scv, submit_rest,
+                               collect_rest, large_n=_large_n_requested(large_n))
+
+        def collect_other(ticket):
+            return ticket.collect() if isinstance(ticket, _TailTicket) else collect_rest(ticket)
+
+        split = _PtileTicket(native, device, problems, itl_arr, tail_arr, scv_arr, submit_other,
+                             collect_other, large_n=_large_n_requested(large_n))
         return split.collect()
     if want_gpu:
         native = get_native()  # raises loudly if missing on a GPU box
@@ -838,16 +1043,20 @@ class SyncDispatch:
     need the M/G/1 correction: ``submit`` then resolves the rows' cs^2
     against it and passes the vector on, so the fleet is sized by the same
     native path as a Markovian one.  ``ttft_tail`` > 0 sizes every row to
-    that TTFT tail probability (``solve_problems(..., ttft_tail=...)``)."""
+    that TTFT tail probability (``solve_problems(..., ttft_tail=...)``), and
+    ``itl_tail`` > 0 to that ITL tail fraction."""
 
     def __init__(self, device: Optional[str], global_scv: Optional[float] = None,
-                 ttft_tail: float = 0.0) -> None:
+                 ttft_tail: float = 0.0, itl_tail: float = 0.0) -> None:
         self.device = device
         self.global_scv = global_scv
         self.ttft_tail = ttft_tail
+        self.itl_tail = itl_tail
 
     def submit(self, problems: np.ndarray, scv_rows=None):
         extra = {"ttft_tail": self.ttft_tail} if self.ttft_tail > 0 else {}
+        if self.itl_tail > 0:
+            extra["itl_tail"] = self.itl_tail
         if self.global_scv is not None:
             scv_arr = _resolved_scv(scv_rows, self.global_scv)
             return solve_problems(problems, self.device, scv=scv_arr, **extra)
@@ -869,18 +1078,38 @@ class NativeGpuDispatch:
     to the waiting-time tail kernel as a second launch (``_TailTicket``) and
     the others through this class's own path, so the chunk stays
     asynchronous; a tail row above GPU_MAX_BATCH_LIMIT is solved on the CPU
-    inside ``submit``."""
+    inside ``submit``.  ``itl_tail`` > 0 sizes every row's ITL target to that
+    tail fraction: the rows with an ITL target go to the percentile kernel
+    (``_PtileTicket``), enqueued first, and the others through this dispatch
+    without it."""
 
     def __init__(self, native, device: str, global_scv: Optional[float] = None,
-                 ttft_tail: float = 0.0) -> None:
+                 ttft_tail: float = 0.0, itl_tail: float = 0.0) -> None:
         self.native = native
         self.device = device
         self.global_scv = global_scv
-        self.ttft_tail = 0.0
+        self.ttft_tail = self.itl_tail = 0.0
         # the mean-TTFT twin: this dispatch (of this class) without the tail,
         # for the rows of a split chunk that carry no TTFT target
         self._mean = copy.copy(self) if ttft_tail > 0 else None
         self.ttft_tail = ttft_tail
+        # the mean-ITL twin: this dispatch without the ITL tail, for the rows
+        # of a split chunk that carry no ITL target
+        self._mean_itl = copy.copy(self) if itl_tail > 0 else None
+        self.itl_tail = itl_tail
+
+    def _submit_ptile(self, problems: np.ndarray, scv_rows, large_n: bool = False):
+        """The chunk as a ``_PtileTicket``; its other rows go through the
+        mean-ITL twin, TTFT tail included."""
+        twin = self._mean_itl
+        scv_arr = None
+        if self.global_scv is not None:
+            scv_arr = _resolved_scv(scv_rows, self.global_scv)
+        n_rows = problems.shape[0]
+        tail_arr = np.full(n_rows, self.ttft_tail) if self.ttft_tail > 0 else None
+        return _PtileTicket(self.native, self.device, problems, np.full(n_rows, self.itl_tail),
+                            tail_arr, scv_arr, lambda rows, scv, _tail: twin.submit(rows, scv),
+                            twin.collect, large_n=large_n), None
 
     def _submit_split(self, problems: np.ndarray, scv_rows, large_n: bool = False):
         """The chunk as a ``_TailTicket``; its other rows go through the
@@ -896,6 +1125,8 @@ class NativeGpuDispatch:
                            mean.submit, mean.collect, large_n=large_n), None
 
     def submit(self, problems: np.ndarray, scv_rows=None):
+        if self.itl_tail > 0:
+            return self._submit_ptile(problems, scv_rows)
         if self.ttft_tail > 0:
             return self._submit_split(problems, scv_rows)
         scv_arr = None
@@ -916,7 +1147,7 @@ class NativeGpuDispatch:
         native_ticket, solved = ticket
         if native_ticket is None:
             return solved
-        if isinstance(native_ticket, _TailTicket):
+        if isinstance(native_ticket, (_TailTicket, _PtileTicket)):
             return native_ticket.collect()
         return self.native.collect(native_ticket)
 
@@ -934,6 +1165,8 @@ class LargeNGpuDispatch(NativeGpuDispatch):
     so the default pipeline runs the class above as it always did."""
 
     def submit(self, problems: np.ndarray, scv_rows=None):
+        if self.itl_tail > 0:
+            return self._submit_ptile(problems, scv_rows, large_n=True)
         if self.ttft_tail > 0:
             return self._submit_split(problems, scv_rows, large_n=True)
         if not problems[:, P_MAX_BATCH].max() <= GPU_MAX_BATCH_LIMIT:  # also a NaN N
@@ -991,17 +1224,22 @@ class BatchedAllocationSolver:
     On the GPU those rows run on the waiting-time tail kernel and their chunk
     stays asynchronous; with ``large_n`` that holds for servers whose max
     batch exceeds GPU_MAX_BATCH_LIMIT too (the compact tail kernel).
+    ``itl_percentile`` does the same for the ITL target (module docstring,
+    "ITL percentile"); ``None`` asks ``WVA_ITL_PERCENTILE``.  On the GPU those
+    rows run on the percentile kernel, which takes their TTFT percentile along.
     """
 
     def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None,
                  large_n: Optional[bool] = None,
-                 ttft_percentile: Optional[float] = None) -> None:
+                 ttft_percentile: Optional[float] = None,
+                 itl_percentile: Optional[float] = None) -> None:
         if chunks is not None and chunks < 1:
             raise ValueError("chunks must be at least 1")
         self.device = device
         self.chunks = chunks
         self.large_n = large_n
         self.ttft_tail = None if ttft_percentile is None else percentile_ttft_tail(ttft_percentile)
+        self.itl_tail = None if itl_percentile is None else percentile_ttft_tail(itl_percentile)
 
     def _plan(self, system: System, servers):
         """The dispatch and chunk count for this fleet, decided before any
@@ -1014,6 +1252,7 @@ class BatchedAllocationSolver:
         )
         dispatch_scv = global_scv if track_scv else None
         tail = self.ttft_tail if self.ttft_tail is not None else configured_ttft_tail()
+        itl = self.itl_tail if self.itl_tail is not None else configured_itl_tail()
         want_gpu = self.device is not None and str(self.device).startswith("cuda")
         if want_gpu and not _graph_requested():
             from . import get_native
@@ -1026,11 +1265,12 @@ class BatchedAllocationSolver:
             if len(servers) * len(system.accelerators) >= _GPU_CHUNKING_ROW_BOUND:
                 chunks = 1
             if _large_n_requested(self.large_n):
-                return LargeNGpuDispatch(native, self.device, dispatch_scv, tail), chunks, track_scv
-            return NativeGpuDispatch(native, self.device, dispatch_scv, tail), chunks, track_scv
+                return (LargeNGpuDispatch(native, self.device, dispatch_scv, tail, itl), chunks,
+                        track_scv)
+            return NativeGpuDispatch(native, self.device, dispatch_scv, tail, itl), chunks, track_scv
         if track_scv:
-            return SyncDispatch(self.device, dispatch_scv, tail), 1, True
-        return SyncDispatch(self.device, ttft_tail=tail), self.chunks or 1, False
+            return SyncDispatch(self.device, dispatch_scv, tail, itl), 1, True
+        return SyncDispatch(self.device, ttft_tail=tail, itl_tail=itl), self.chunks or 1, False
 
     def _predict_percentiles(self, jobs, eps: float, global_scv: Optional[float]) -> None:
         """``ttft_percentile`` of every allocation in ``jobs``: its row at the
