@@ -389,6 +389,36 @@ class QueueAnalyzer:
         slow = decode.alpha + decode.beta * batch.astype(np.float64) > target_itl
         return float(tokens[slow].sum() / tokens.sum())
 
+    def itl_quantile(self, request_rate: float, eps: float) -> float:
+        """The inter-token latency (ms) that a fraction ``eps`` of the tokens
+        emitted at ``request_rate`` (req/s) exceeds: ``eps = 0.05`` is the p95
+        ITL.
+
+        The inverse of ``itl_exceedance`` at a fixed rate and the specification
+        of every native implementation (csrc/queue_core.h, "ITL quantile").
+        With ``S_b`` the share of tokens emitted in decode steps with more than
+        b requests in service (``itl_exceedance``'s token weights; 0 for b =
+        N), which never grows with b,
+
+            b* = min{b in 1..N : S_b <= eps},   q = decode_time(b*).
+
+        It is stated on the batch count, not on decode times, so ``beta = 0``
+        and ``N = 1`` are no special cases.  The service-time cs^2 plays no
+        part.  Raises :class:`AnalyzerError` for an ``eps`` outside the open
+        (0, 1) and for a rate ``analyze`` rejects."""
+        if not 0.0 < eps < 1.0:  # also fails NaN
+            raise AnalyzerError(f"invalid ITL tail fraction {eps}")
+        if not 0.0 < request_rate <= self.rate_range.max:  # also fails NaN
+            raise AnalyzerError(f"invalid request rate {request_rate}")
+        m = self._solve(request_rate / 1000.0)
+        N, K = self.max_batch_size, self.model.K
+        batch = np.minimum(np.arange(1, K + 1), N)
+        tokens = m.p[1:] * self.serv_rate[batch - 1]  # [n - 1]: state n
+        above = np.cumsum(tokens[::-1])[::-1]  # [b]: the states n > b, summed from the top
+        meets = np.flatnonzero(above[1:N] <= eps * above[0])  # [b - 1], b < N
+        b = int(meets[0]) + 1 if meets.size else N
+        return self.service_parms.decode.decode_time(float(b))
+
     # -- public API ---------------------------------------------------------
     def analyze(self, request_rate: float) -> AnalysisMetrics:
         """Evaluate performance metrics at a given request rate (req/s)."""

@@ -48,6 +48,7 @@ class Allocation:
     __slots__ = (
         "accelerator", "num_replicas", "batch_size", "cost", "value",
         "itl", "ttft", "rho", "max_arrv_rate_per_replica", "_ttft_percentile",
+        "_itl_percentile",
     )
 
     def __init__(
@@ -87,6 +88,22 @@ class Allocation:
     def ttft_percentile(self, value: float) -> None:
         self._ttft_percentile = value
 
+    @property
+    def itl_percentile(self) -> float:
+        """Predicted ITL (ms) at the sizing percentile (WVA_ITL_PERCENTILE) at
+        this allocation's per-replica rate: the decode time of the batch count
+        that all but that share of the tokens stay within.  0.0 unless sized to
+        an ITL percentile; the slot stays unset until somebody assigns, as for
+        ``ttft_percentile``."""
+        try:
+            return self._itl_percentile
+        except AttributeError:
+            return 0.0
+
+    @itl_percentile.setter
+    def itl_percentile(self, value: float) -> None:
+        self._itl_percentile = value
+
     # -- accessors mirroring the reference API ------------------------------
     def set_value(self, value: float) -> None:
         self.value = value
@@ -119,6 +136,8 @@ class Allocation:
         a.value = self.value
         if self.ttft_percentile != 0.0:
             a.ttft_percentile = self.ttft_percentile
+        if self.itl_percentile != 0.0:
+            a.itl_percentile = self.itl_percentile
         return a
 
     def allocation_data(self) -> AllocationData:
@@ -232,10 +251,16 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
     # WVA_TTFT_PERCENTILE: size to that percentile of TTFT, not to its mean;
     # WVA_ITL_PERCENTILE: the same for ITL
     ttft_tail = configured_ttft_tail()
+    itl_tail = configured_itl_tail()
     target_perf = TargetPerf(
         target_ttft=target.ttft, target_itl=target.itl, target_tps=target.tps,
-        ttft_tail=ttft_tail, itl_tail=configured_itl_tail(),
+        ttft_tail=ttft_tail, itl_tail=itl_tail,
     )
+    # The ITL percentile is predicted for a server that was sized to it: the
+    # knob is set and the target has an ITL target.  Without an ITL target the
+    # knob moved nothing, and itl_percentile stays 0.0.  (ttft_percentile is
+    # predicted whenever its knob is set, TTFT target or not.)
+    predict_itl = itl_tail > 0 and target.itl > 0
     try:
         _, metrics, _ = qa.size(target_perf)
     except AnalyzerError:
@@ -259,6 +284,7 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
         metrics = qa.analyze(rate)
         # sized to a percentile: predict that percentile too, not the mean alone
         ttft_percentile = qa.ttft_quantile(rate, ttft_tail) if ttft_tail > 0 else 0.0
+        itl_percentile = qa.itl_quantile(rate, itl_tail) if predict_itl else 0.0
     except AnalyzerError:
         return None
 
@@ -274,6 +300,8 @@ def create_allocation(system: "System", server_name: str, acc_name: str) -> Opti
     )
     if ttft_tail > 0:
         alloc.ttft_percentile = ttft_percentile
+    if predict_itl:
+        alloc.itl_percentile = itl_percentile
     alloc.set_value(alloc.cost)
     return alloc
 

@@ -1006,6 +1006,91 @@ WVA_HD double occupancy_tail(const OccupancySweep &w, double all, double upper) 
   return fmin(fmax((upper + w.geo) / (all + w.geo), 0.0), 1.0);
 }
 
+// ---------------------------------------------------------------------------
+// ITL quantile: the inverse of the occupancy tail at a fixed rate.  Given a
+// per-replica rate rho (req/s) and a token share eps, the ITL that a fraction
+// eps of the tokens exceeds (eps = 0.05: the p95 ITL).
+//
+// With lam = rho / 1000 and, for a batch count b in 1..N, S_b the share of
+// tokens emitted in decode steps with MORE than b requests in service, the
+// detailed balance of "Occupancy tail" gives
+//
+//   S_b = sum_{j=b..K-1} pi_j,  pi_j = p[j] / (1 - p[K]),  b < N;   S_N = 0,
+//
+// non-increasing in b, and
+//
+//   b*    = min { b in 1..N : S_b <= eps },
+//   q_itl = decode_time(b*) = alpha + beta * b*.
+//
+// It is stated on the batch index, not on a comparison of decode times, so
+// beta = 0 and N = 1 are no special cases of the definition (both give alpha +
+// beta).  The wait scale plays no part: occupancy does not depend on it.
+//
+// Evaluation.  lam is fixed, so this is the inverse of a step function: ONE
+// sweep over the pre-batch states and a scan, not a search.  Relative to e^m
+// (occupancy_sweep_of), with e_j = exp(log_p(j) - m), G the states N+1..K-1
+// and A = sum_{j=0..N} e_j,
+//
+//   T_b = G + sum_{j=b..N} e_j,   S_b = T_b / (A + G) for b < N,
+//
+// and with b_f the last b in 0..N-1 whose T_b exceeds eps (A + G) (b_f = 0 at
+// least: T_0 = A + G and eps < 1), b* = max(b_f + 1, 1): itl_quantile_batch.
+// T is summed directly from the top, all terms positive, never as 1 - prefix,
+// for the reason given under "Occupancy tail".  b* = N needs no S at all, so
+// N = 1 evaluates nothing; that is also what keeps geo_tail from declining
+// (N >= 2 and lam <= lam_max give (10 N - 1) |d| >= 0.019, as above; at N = 1
+// it would decline near lam_max).
+//
+// The result row is that of the TTFT quantile, (valid, q), under the same
+// rules without a cs^2: (0, 0) for a row that fails row_valid, an eps that is
+// no finite number in the open (0, 1), or a rate that is NaN, +-inf, <= 0 or
+// above lam_max * 1000 (quantile_inputs_valid).
+// ---------------------------------------------------------------------------
+constexpr int Q_ITL = Q_TTFT;  // column 1 of an ITL quantile row
+
+// e_j of a sweep
+WVA_HD double occupancy_term(const OccupancySweep &w, const double *cum, int N, double log_mu_n,
+                             int j) {
+  return exp(log_p_compact(cum, N, log_mu_n, w.loglam, j) - w.m);
+}
+
+// b* from b_f, the last state whose suffix mass exceeds eps (A + G).  A b_f
+// of N (T_N = G + e_N is a mass, not S_N = 0) means b* = N like N - 1 does,
+// and -1 (nothing above, which only rounding could produce) means 1.
+WVA_HD int itl_quantile_batch(int last_above, int N) {
+  const int b = last_above + 1;
+  return b < 1 ? 1 : (b > N ? N : b);
+}
+
+// The serial host reference: b* of a valid row at lam (req/ms) over the
+// compact table.  One sweep from the top, the running suffix mass starting
+// from G and stored for the states below N (suffix must hold N doubles), then
+// a bisection over the stored values, which never decrease towards 0 (adding
+// a positive term never lowers a rounded sum).
+inline int itl_quantile_row(const Parms &p, const double *cum, double log_mu_n, double lam,
+                            double eps, double *suffix) {
+  const int N = p.max_batch;
+  if (N == 1) return 1;
+  const OccupancySweep w = occupancy_sweep_of(p, cum, log_mu_n, lam);
+  double run = w.geo;
+  for (int j = N; j >= 0; --j) {
+    run += occupancy_term(w, cum, N, log_mu_n, j);
+    if (j < N) suffix[j] = run;
+  }
+  const double thresh = eps * run;  // eps (A + G)
+  // first j in [0, N] with suffix[j] <= thresh (N: none); b_f is the one before
+  int lo = 0, hi = N;
+  while (lo < hi) {
+    const int mid = lo + (hi - lo) / 2;
+    if (suffix[mid] > thresh) {
+      lo = mid + 1;
+    } else {
+      hi = mid;
+    }
+  }
+  return itl_quantile_batch(lo - 1, N);
+}
+
 // Whether an evaluator offers itl_exceedance(lam, c) next to eval(lam), and
 // itl_eps(), the row's itl_tail; one that does not sizes to the mean ITL alone,
 // and the callers route no row with itl_tail > 0 to it.

@@ -228,6 +228,22 @@ inline void quantile_one_compact(const double *pr, double rate, double eps, doub
   out[Q_TTFT] = quantile_ttft(p, q, t);
 }
 
+// ITL quantile of one row (queue_core.h, "ITL quantile"): the compact table,
+// then itl_quantile_row's one sweep and scan at the row's rate.  cum and suffix
+// must each hold N doubles (row_compact_length); out gets (valid, q).  No cs^2:
+// occupancy does not depend on the wait scale.
+inline void itl_quantile_one(const double *pr, double rate, double eps, double *out, double *cum,
+                             double *suffix) {
+  out[Q_VALID] = out[Q_ITL] = 0.0;
+  if (!row_valid(pr)) return;
+  const Parms p = parms_from_problem(pr);
+  if (!quantile_inputs_valid(p, rate, eps)) return;
+  const HostCompactTable table(p, cum);
+  const int b = itl_quantile_row(p, cum, table.log_mu_n, rate / 1000.0, eps, suffix);
+  out[Q_VALID] = 1.0;
+  out[Q_ITL] = decode_time(p, (double)b);
+}
+
 // Length of the log-factorial table quantile_one needs for a batch: 10 * N of
 // its largest valid row.
 inline long long quantile_tail_length(const double *pr, long long rows) {

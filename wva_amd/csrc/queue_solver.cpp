@@ -239,6 +239,33 @@ static torch::Tensor ttft_quantiles(torch::Tensor problems, torch::Tensor rates,
   return out;
 }
 
+// The ITL quantile of every row at its own rate and eps (queue_core.h, "ITL
+// quantile"), on the host: [B, 12] problems, float64 [B] rates (req/s per
+// replica) and eps -> [B, 2] (valid, q).  CPU tensors only; on the GPU the ITL
+// quantile kernel is reached through submit_itl_quantile.
+static torch::Tensor itl_quantiles(torch::Tensor problems, torch::Tensor rates,
+                                   torch::Tensor eps) {
+  check_problems(problems);
+  TORCH_CHECK(!problems.is_cuda(), "itl_quantiles takes CPU tensors");
+  problems = problems.contiguous();
+  const int64_t B = problems.size(0);
+  auto out = torch::zeros({B, (int64_t)wva::QUANTILE_FIELDS}, problems.options());
+  const double *rate_ptr = scv_data(rates, problems, "rates");
+  const double *eps_ptr = scv_data(eps, problems, "eps");
+  if (B == 0) return out;
+  const double *pr = problems.data_ptr<double>();
+  double *res = out.data_ptr<double>();
+  const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
+  at::parallel_for(0, B, 1, [&](int64_t begin, int64_t end) {
+    std::vector<double> cum((size_t)table_len), suffix((size_t)table_len);
+    for (int64_t i = begin; i < end; ++i) {
+      wva::itl_quantile_one(pr + i * wva::PROBLEM_FIELDS, rate_ptr[i], eps_ptr[i],
+                            res + i * wva::QUANTILE_FIELDS, cum.data(), suffix.data());
+    }
+  });
+  return out;
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "wva_amd native batched queue solver (CPU + gfx950 HIP)";
   m.def("solve_allocations", &solve_allocations,
@@ -270,6 +297,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "compact quantile kernel",
         pybind11::arg("problems"), pybind11::arg("rates"), pybind11::arg("eps"),
         pybind11::arg("scv") = pybind11::none());
+  m.def("itl_quantiles", &itl_quantiles,
+        "The ITL a share eps of each row's tokens exceeds at its per-replica rate "
+        "(req/s), on the CPU: float64 [B, 2] of (valid, q in ms)",
+        pybind11::arg("problems"), pybind11::arg("rates"), pybind11::arg("eps"));
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
   // greedy_solve, HAS_GREEDY
@@ -316,6 +347,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "reserves LDS for (N doubles, up to ~7800)",
         pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("rates"),
         pybind11::arg("eps"), pybind11::arg("scv") = pybind11::none());
+  m.def("submit_itl_quantile", &wva::dispatch::submit_itl_quantile,
+        "submit through the ITL quantile kernel: rates (req/s per replica) and eps "
+        "are float64 [B] vectors; max_n is the largest max batch N the launch "
+        "reserves LDS for (N doubles, up to 7872); collect returns [B, 2] of "
+        "(valid, q in ms) for such a ticket",
+        pybind11::arg("problems"), pybind11::arg("max_n"), pybind11::arg("rates"),
+        pybind11::arg("eps"));
   m.def("submit_ptile", &wva::dispatch::submit_ptile,
         "submit through the percentile kernel: rows whose ITL target is sized on "
         "the occupancy tail, itl_tail the float64 [B] vector of their allowed "
@@ -328,7 +366,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("split") = false);
   m.def("collect", &wva::dispatch::collect,
         "Wait (GIL released) for a ticket and return its float64 results: [B, 6], "
-        "or [B, 2] for a submit_quantile or submit_quantile_compact ticket",
+        "or [B, 2] for a submit_quantile, submit_quantile_compact or "
+        "submit_itl_quantile ticket",
         pybind11::arg("ticket"));
   m.def("dispatch_pool_stats", &wva::dispatch::pool_stats,
         "(slots, slots in flight) of the dispatch pool");

@@ -138,6 +138,40 @@ static py::array_t<double> ttft_quantiles(
   return out;
 }
 
+// The ITL quantile of every row at its own rate and eps (queue_core.h, "ITL
+// quantile"): [B, 12] problems, float64 [B] rates (req/s per replica) and eps
+// -> [B, 2] (valid, q).  No cs^2 vector: occupancy does not depend on it.
+static py::array_t<double> itl_quantiles(
+    py::array_t<double, py::array::c_style | py::array::forcecast> problems, py::object rates,
+    py::object eps) {
+  auto buf = problems.request();
+  if (buf.ndim != 2 || buf.shape[1] != (ssize_t)wva::PROBLEM_FIELDS)
+    throw std::invalid_argument("problems must be [B, 12] float64");
+  const ssize_t B = buf.shape[0];
+  if (rates.is_none() || eps.is_none()) throw py::type_error("rates and eps must be float64 arrays");
+  const double *rate_ptr = wva::row_vector_data(rates, B, "rates");
+  const double *eps_ptr = wva::row_vector_data(eps, B, "eps");
+  auto out = py::array_t<double>({B, (ssize_t)wva::QUANTILE_FIELDS});
+  const double *pr = (const double *)buf.ptr;
+  double *res = (double *)out.request().ptr;
+  if (B == 0) return out;
+
+  const int table_len = wva::batch_table_length<wva::HostCompactTable>(pr, B);
+  {
+    py::gil_scoped_release release;
+#pragma omp parallel
+    {
+      std::vector<double> cum((size_t)table_len), suffix((size_t)table_len);
+#pragma omp for schedule(dynamic, 8)
+      for (ssize_t i = 0; i < B; ++i) {
+        wva::itl_quantile_one(pr + i * wva::PROBLEM_FIELDS, rate_ptr[i], eps_ptr[i],
+                              res + i * wva::QUANTILE_FIELDS, cum.data(), suffix.data());
+      }
+    }
+  }
+  return out;
+}
+
 PYBIND11_MODULE(_queue_native_cpu, m) {
   m.doc() = "wva_amd torch-free batched queue solver (CPU/OpenMP)";
   m.def("solve_allocations", &solve_allocations<wva::HostFullTable>,
@@ -166,6 +200,10 @@ PYBIND11_MODULE(_queue_native_cpu, m) {
         "ttft_quantiles without a log-factorial table: the host reference of the "
         "compact quantile kernel",
         py::arg("problems"), py::arg("rates"), py::arg("eps"), py::arg("scv") = py::none());
+  m.def("itl_quantiles", &itl_quantiles,
+        "The ITL a share eps of each row's tokens exceeds at its per-replica rate "
+        "(req/s): float64 [B, 2] of (valid, q in ms)",
+        py::arg("problems"), py::arg("rates"), py::arg("eps"));
   m.attr("PROBLEM_FIELDS") = (int)wva::PROBLEM_FIELDS;
   m.attr("RESULT_FIELDS") = (int)wva::RESULT_FIELDS;
   // limited-mode greedy solve (greedy_core.h): greedy_solve, HAS_GREEDY

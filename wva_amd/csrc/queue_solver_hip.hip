@@ -70,7 +70,9 @@ namespace wva {
 // namespace), and a tenth answers it without a table of the tail sum, for N up
 // to the compact limit (the compact quantile kernel behind it).  An eleventh
 // sizes a row's ITL target to a percentile as well (the percentile kernel
-// behind the compact waiting-time tail kernel, whose TTFT side it reuses).
+// behind the compact waiting-time tail kernel, whose TTFT side it reuses).  A
+// twelfth answers the quantile question for the ITL (the ITL quantile kernel,
+// last in the namespace): one sweep and a scan, no search.
 
 // Reduction scratch layout (doubles, after cum[max_k] in dynamic LDS):
 //   red[0..WAVES*5-1]  per-wave partials (S, Ni, Snum, Ninum, eK)
@@ -1411,6 +1413,175 @@ extern "C" __global__ void __launch_bounds__(kQuantileThreads) wva_quantile_kern
   quantile_body<ChainTerms>(prob, scv, rates, eps_vec, out, n_problems, max_n);
 }
 
+// ---------------------------------------------------------------------------
+// ITL quantile kernel: the ITL that a share eps of a row's tokens exceeds at a
+// given per-replica rate (queue_core.h, "ITL quantile"): b*, the first batch
+// count whose upper occupancy mass T_b is within eps of the whole mass, and
+// decode_time(b*).  Lambda is fixed, so this inverts a step function: one
+// sweep of the N + 1 pre-batch states and a scan, where a bisection over b
+// with occupancy_sums would pay about log2 N whole exp sweeps (13 at N =
+// 7680).  An exp is evaluated N + 1 times in phase B and 64 times in phase D.
+// One workgroup of 256 threads per row, workgroup barriers only, and one
+// kernel for N = 1 .. 7872: nothing but cum[0..N-1] is tabulated.
+//
+// LDS (doubles): cum[max_n]; totals[256], the scan's chunk totals and then the
+// tile masses (at most 124 of them); none of the 64 slack doubles is used.
+// max_n + 256 + 64 in all, the compact kernels' footprint.
+//
+// Row guard, as quantile_body: threads 0 and 1 store the zero row, then the
+// row contract (no cs^2: 1.0), trunc(N) <= max_n and quantile_inputs_valid end
+// the workgroup before LDS is touched.  N = 1 ends it there as well, at (1,
+// decode_time(1)): b* = N needs no mass (and geo_tail would decline).
+//
+// Phase A.  build_cum<256> over the compact table (two barriers), then
+// occupancy_sweep_of at lam = rate / 1000: the log reference m and the
+// geometric mass G of the states N+1..K-1, scalar and uniform.
+//
+// Phase B, tile masses.  The states 0..N are cut into tiles of 64 consecutive
+// states.  Wave w takes tiles w, w + 4, ..., two per pass so that two
+// independent exp chains are in flight; lane l evaluates e = exp(log_p(64
+// tile + l) - m), consecutive lanes reading consecutive cum entries
+// (conflict-free); a __shfl_down reduction, and lane 0 writes the tile's mass
+// to totals[tile].  The last tile is partly filled: a lane past N contributes
+// 0.  One barrier follows, the kernel's third and last; build_cum's closing
+// barrier is what freed totals, and waves 1..3 end behind this one.
+//
+// Phase C, locate (wave 0).  Lane l holds the masses of tiles 2 l and 2 l + 1
+// (at most 124 tiles).  An inclusive suffix scan of the pair sums over the
+// lanes (__shfl_down by 1, 2, .. 32), G added on top, gives each tile the
+// mass above it and, at lane 0, the whole mass A + G.  The mass above a tile
+// comes from the NEXT lane's suffix, never from a subtraction: it may be
+// 1e-20 of the pair.  The crossing tile is the last one whose mass from its
+// first state up exceeds eps (A + G): one __ballot over the lanes' candidates.
+//
+// Phase D, resolve (wave 0).  The crossing tile's 64 states are evaluated
+// again, one per lane, scanned the same way on top of the mass above the tile,
+// and b_f, the last state whose T_b exceeds the threshold, is the highest bit
+// of a __ballot; itl_quantile_batch turns it into b* (N when T_{N-1} is still
+// above, 1 when T_1 already is not).  Should rounding leave no such state in
+// the tile phase C picked, b_f is the state before the tile.  Threads 0 and 1,
+// which stored the zero row, store (1, decode_time(b*)).
+//
+// The tile-wise split was kept over a strided sweep (thread tid taking states
+// tid, tid + 256, ..) because a strided partial is no suffix of anything: the
+// locate step would then need the per-state masses in LDS, N more doubles.
+// ---------------------------------------------------------------------------
+constexpr int kItlQuantileThreads = 256;
+constexpr int kOccupancyTile = 64;  // one state per lane of a wave
+
+// e of state 64 tile + lane, 0 past N (the read stays inside cum either way)
+__device__ inline double occupancy_tile_term(const OccupancySweep &w, const LdsCompactTable &table,
+                                             int tile, int lane) {
+  const int s = tile * kOccupancyTile + lane;
+  const double e =
+      occupancy_term(w, table.cum, table.N, table.log_mu_n, s <= table.N ? s : table.N);
+  return s <= table.N ? e : 0.0;
+}
+
+// inclusive suffix sum over the lanes of a wave: lane l gets v_l + .. + v_63
+__device__ inline double wave_suffix_sum(double v, int lane) {
+  for (int off = 1; off < 64; off <<= 1) {
+    const double up = __shfl_down(v, off, 64);
+    v += lane + off < 64 ? up : 0.0;
+  }
+  return v;
+}
+
+__device__ void itl_quantile_body(const double *__restrict__ prob,
+                                  const double *__restrict__ rates,
+                                  const double *__restrict__ eps_vec, double *__restrict__ out,
+                                  int n_problems, int max_n) {
+  constexpr int THREADS = kItlQuantileThreads;
+  constexpr int WAVES = THREADS / 64;
+  const int pid = blockIdx.x;
+  if (pid >= n_problems) return;
+  const double *pr = prob + (size_t)pid * PROBLEM_FIELDS;
+  double *res = out + (size_t)pid * QUANTILE_FIELDS;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+
+  const double rate = rates[pid];
+  const double eps = eps_vec[pid];
+  if (tid < QUANTILE_FIELDS) res[tid] = 0.0;
+  if (row_rejected<LdsCompactTable>(pr, 1.0, max_n)) return;
+  const Parms p = parms_from_problem(pr);
+  if (!quantile_inputs_valid(p, rate, eps)) return;  // uniform: one row per workgroup
+  const int N = p.max_batch;
+  if (N == 1) {
+    if (tid < QUANTILE_FIELDS) res[tid] = (tid == Q_VALID) ? 1.0 : decode_time(p, 1.0);
+    return;
+  }
+
+  extern __shared__ double smem[];
+  double *cum = smem;             // this row's N entries
+  double *totals = smem + max_n;  // THREADS chunk totals, then the tile masses
+
+  // Phase A
+  const LdsCompactTable table(p, cum);
+  build_cum<THREADS>(p, table.scan_length(), cum, totals);
+  const OccupancySweep w = occupancy_sweep_of(p, cum, table.log_mu_n, rate / 1000.0);
+
+  // Phase B
+  const int n_tiles = N / kOccupancyTile + 1;  // the states 0..N
+  static_assert((64 * 1024 / 8 - THREADS - 64) / kOccupancyTile + 1 <= 2 * 64 &&
+                    2 * 64 <= THREADS,
+                "wave 0 holds two tiles per lane, and totals holds them all");
+  int tile = wave;
+  for (; tile + WAVES < n_tiles; tile += 2 * WAVES) {
+    double e = occupancy_tile_term(w, table, tile, lane);
+    double e2 = occupancy_tile_term(w, table, tile + WAVES, lane);
+    for (int off = 32; off > 0; off >>= 1) {
+      e += __shfl_down(e, off, 64);
+      e2 += __shfl_down(e2, off, 64);
+    }
+    if (lane == 0) {
+      totals[tile] = e;
+      totals[tile + WAVES] = e2;
+    }
+  }
+  if (tile < n_tiles) {
+    double e = occupancy_tile_term(w, table, tile, lane);
+    for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
+    if (lane == 0) totals[tile] = e;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+
+  // Phase C
+  const int t0 = 2 * lane, t1 = 2 * lane + 1;
+  const double m0 = t0 < n_tiles ? totals[t0] : 0.0;
+  const double m1 = t1 < n_tiles ? totals[t1] : 0.0;
+  const double suffix = wave_suffix_sum(m0 + m1, lane);
+  const double thresh = eps * (w.geo + __shfl(suffix, 0, 64));  // eps (A + G)
+  const double next = __shfl_down(suffix, 1, 64);
+  const double above1 = w.geo + (lane < 63 ? next : 0.0);  // the mass above tile t1
+  const double above0 = above1 + m1;                       // above tile t0; t1 from its first state
+  int candidate = -1;
+  if (t0 < n_tiles && above0 + m0 > thresh) candidate = t0;
+  if (t1 < n_tiles && above0 > thresh) candidate = t1;
+  const unsigned long long holders = __ballot(candidate >= 0);
+  const int owner = holders != 0ull ? 63 - __clzll((long long)holders) : 0;
+  int crossing = __shfl(candidate, owner, 64);
+  if (crossing < 0) crossing = 0;  // eps (A + G) < A + G: only rounding gets here
+  const double above = __shfl((crossing & 1) ? above1 : above0, owner, 64);
+
+  // Phase D
+  const int s = crossing * kOccupancyTile + lane;
+  const double in_tile = wave_suffix_sum(occupancy_tile_term(w, table, crossing, lane), lane);
+  const unsigned long long over = __ballot((s <= N) & (above + in_tile > thresh));
+  const int last_above = crossing * kOccupancyTile +
+                         (over != 0ull ? 63 - __clzll((long long)over) : -1);
+  const int b_star = itl_quantile_batch(last_above, N);
+  if (tid < QUANTILE_FIELDS) res[tid] = (tid == Q_VALID) ? 1.0 : decode_time(p, (double)b_star);
+}
+
+extern "C" __global__ void __launch_bounds__(kItlQuantileThreads) wva_itl_quantile_kernel(
+    const double *__restrict__ prob, const double *__restrict__ rates,
+    const double *__restrict__ eps_vec, double *__restrict__ out, int n_problems, int max_n) {
+  itl_quantile_body(prob, rates, eps_vec, out, n_problems, max_n);
+}
+
 }  // namespace wva
 
 #include <cstdlib>
@@ -1594,5 +1765,23 @@ extern "C" int wva_launch_quantile_compact(const double *prob, const double *scv
   hipLaunchKernelGGL(wva::wva_quantile_kernel_compact, dim3(n_problems),
                      dim3(wva::kQuantileThreads), smem, (hipStream_t)stream, prob, scv, rates,
                      eps, out, n_problems, max_n);
+  return (int)hipGetLastError();
+}
+
+// ITL quantile launch: rates (req/s per replica) and eps are device vectors of
+// n_problems doubles, both required; max_n is the largest trunc(N) the launch
+// reserves LDS for, cum[max_n] alone.  -1, and nothing launched, without either
+// vector or when max_n + 256 + 64 doubles exceed 64 KiB (max_n beyond 7872).
+extern "C" int wva_launch_itl_quantile(const double *prob, const double *rates,
+                                       const double *eps, double *out, int n_problems,
+                                       int max_n, void *stream) {
+  if (rates == nullptr || eps == nullptr || max_n < 1 ||
+      !fits_lds(max_n, wva::kItlQuantileThreads)) {
+    return -1;
+  }
+  const size_t smem = (size_t)(max_n + wva::kItlQuantileThreads + 64) * sizeof(double);
+  hipLaunchKernelGGL(wva::wva_itl_quantile_kernel, dim3(n_problems),
+                     dim3(wva::kItlQuantileThreads), smem, (hipStream_t)stream, prob, rates, eps,
+                     out, n_problems, max_n);
   return (int)hipGetLastError();
 }

@@ -26,7 +26,8 @@
 // vector, the rows' ttft_tail, behind that, in the same upload.  A
 // submit_quantile or submit_quantile_compact carries two, the rows' eps and
 // per-replica rates, and its result rows are 2 doubles wide, not 6: the slot
-// remembers the width for collect.  A submit_ptile carries the rows' itl_tail
+// remembers the width for collect; a submit_itl_quantile carries the same two
+// and no cs^2.  A submit_ptile carries the rows' itl_tail
 // in that last place, behind the optional cs^2 and ttft_tail: still one upload,
 // and nullptr for a vector that is absent.
 //
@@ -84,6 +85,9 @@ extern "C" int wva_launch_quantile(const double *prob, const double *scv, const 
 extern "C" int wva_launch_quantile_compact(const double *prob, const double *scv,
                                            const double *rates, const double *eps, double *out,
                                            int n_problems, int max_n, void *stream);
+extern "C" int wva_launch_itl_quantile(const double *prob, const double *rates,
+                                       const double *eps, double *out, int n_problems,
+                                       int max_n, void *stream);
 
 namespace wva {
 namespace dispatch {
@@ -404,6 +408,26 @@ inline int64_t submit_quantile_compact(py::array problems, int64_t max_n, py::ob
       },
       problems, max_n, scv, "the compact quantile kernel cannot hold ",
       " states in LDS (max_batch limit ~7800); use the CPU path for these problems", eps, rates,
+      QUANTILE_FIELDS);
+}
+
+// through the ITL quantile kernel (queue_core.h, "ITL quantile"): rates is the
+// [B] vector of per-replica rates (req/s) and eps that of the token shares,
+// both required, and there is no cs^2; max_n is the largest max batch N the
+// launch reserves LDS for (N doubles, up to 7872).  The ticket's results are
+// [B, 2]: (valid, q).
+inline int64_t submit_itl_quantile(py::array problems, int64_t max_n, py::object rates,
+                                   py::object eps) {
+  if (rates.is_none() || eps.is_none()) {
+    throw py::type_error("rates and eps must be float64 arrays");
+  }
+  return submit_with(
+      [](const double *prob, const double *, const double *eps_vec, const double *rate_vec,
+         double *out, int n, int len, void *stream) {
+        return wva_launch_itl_quantile(prob, rate_vec, eps_vec, out, n, len, stream);
+      },
+      problems, max_n, py::none(), "the ITL quantile kernel cannot hold ",
+      " states in LDS (max_batch limit 7872); use the CPU path for these problems", eps, rates,
       QUANTILE_FIELDS);
 }
 

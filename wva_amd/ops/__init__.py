@@ -85,9 +85,11 @@ def get_native():
 from .batched import (  # noqa: E402
     GPU_COMPACT_MAX_BATCH_LIMIT,
     GPU_MAX_BATCH_LIMIT,
+    Q_ITL,
     Q_TTFT,
     Q_VALID,
     BatchedAllocationSolver,
+    itl_quantiles,
     solve_problems,
     ttft_quantiles,
 )
@@ -100,8 +102,10 @@ __all__ = [
     "BatchedAllocationSolver",
     "solve_problems",
     "ttft_quantiles",
+    "itl_quantiles",
     "Q_VALID",
     "Q_TTFT",
+    "Q_ITL",
     "GPU_MAX_BATCH_LIMIT",
     "GPU_COMPACT_MAX_BATCH_LIMIT",
 ]

@@ -127,6 +127,22 @@ solve with an ``itl_tail`` vector (``_PtileTicket``):
   ``solve_allocations_ptile`` on the CPU while the launches run;
 - every other row: the route it takes without the vector; an invalid eps
   gives the all-zero row.
+
+ITL quantile.  The ITL each allocation's tokens exceed at that share is
+predicted afterwards, by ``itl_quantiles`` (one call per cycle), for the rows
+with an ITL target: with ``S_b`` the share of tokens emitted in decode steps
+with more than b requests in service, ``b* = min{b in 1..N : S_b <= eps}`` and
+the quantile is ``decode_time(b*)``; ``QueueAnalyzer.itl_quantile`` is the
+definition.  The rate is fixed, so the native paths find b* in one sweep over
+the states and a scan, without a search.  There is no ``scv``.  Its routes on
+the GPU:
+
+- N <= 700: ``submit_itl_quantile``, one launch; invalid rows ride along;
+- 700 < N <= 7680, ``large_n`` on, not under ``WVA_GPU_GRAPH=1``: a second
+  ``submit_itl_quantile`` launch that reserves LDS for those rows alone,
+  enqueued before anything is collected;
+- the same with ``large_n`` off (the default), or N > 7680: native CPU solver
+  while the launches run.
 """
 
 from __future__ import annotations
@@ -171,6 +187,8 @@ RESULT_FIELDS = 6
 # TTFT quantile in ms (0 is a legitimate one)
 Q_VALID, Q_TTFT = range(2)
 QUANTILE_FIELDS = 2
+# an itl_quantiles row has the same shape: the ITL quantile in ms in column 1
+Q_ITL = Q_TTFT
 
 # the GPU path keeps the cumulative table in LDS: N <= ~700
 GPU_MAX_BATCH_LIMIT = 700
@@ -911,6 +929,22 @@ def solve_problems(
     return _solve_problems_python(problems, scv=scv_arr)
 
 
+def _row_analyzer(row, scv: float = 1.0) -> QueueAnalyzer:
+    """The ``QueueAnalyzer`` of a row that passed ``valid_rows``."""
+    N = int(row[P_MAX_BATCH])
+    config = Configuration(
+        max_batch_size=N,
+        max_queue_size=N * MAX_QUEUE_TO_BATCH_RATIO,
+        service_parms=ServiceParms(
+            prefill=PrefillParms(gamma=row[P_GAMMA], delta=row[P_DELTA]),
+            decode=DecodeParms(alpha=row[P_ALPHA], beta=row[P_BETA]),
+        ),
+    )
+    size = RequestSize(avg_input_tokens=int(row[P_IN_TOKENS]),
+                       avg_output_tokens=int(row[P_OUT_TOKENS]))
+    return QueueAnalyzer(config, size, scv=scv)
+
+
 def _ttft_quantiles_python(problems, rates, eps, scv) -> np.ndarray:
     """``ttft_quantiles`` row by row through ``QueueAnalyzer.ttft_quantile``,
     the semantic reference; a rejected row is ``(0, 0)``."""
@@ -919,20 +953,24 @@ def _ttft_quantiles_python(problems, rates, eps, scv) -> np.ndarray:
     for i, row in enumerate(problems):
         if not valid[i]:
             continue
-        N = int(row[P_MAX_BATCH])
-        config = Configuration(
-            max_batch_size=N,
-            max_queue_size=N * MAX_QUEUE_TO_BATCH_RATIO,
-            service_parms=ServiceParms(
-                prefill=PrefillParms(gamma=row[P_GAMMA], delta=row[P_DELTA]),
-                decode=DecodeParms(alpha=row[P_ALPHA], beta=row[P_BETA]),
-            ),
-        )
-        size = RequestSize(avg_input_tokens=int(row[P_IN_TOKENS]),
-                           avg_output_tokens=int(row[P_OUT_TOKENS]))
         try:
-            qa = QueueAnalyzer(config, size, scv=float(scv[i]))
+            qa = _row_analyzer(row, float(scv[i]))
             out[i] = 1.0, qa.ttft_quantile(float(rates[i]), float(eps[i]))
+        except AnalyzerError:
+            continue
+    return out
+
+
+def _itl_quantiles_python(problems, rates, eps) -> np.ndarray:
+    """``itl_quantiles`` row by row through ``QueueAnalyzer.itl_quantile``,
+    the semantic reference; a rejected row is ``(0, 0)``."""
+    out = np.zeros((problems.shape[0], QUANTILE_FIELDS), dtype=np.float64)
+    valid = valid_rows(problems)
+    for i, row in enumerate(problems):
+        if not valid[i]:
+            continue
+        try:
+            out[i] = 1.0, _row_analyzer(row).itl_quantile(float(rates[i]), float(eps[i]))
         except AnalyzerError:
             continue
     return out
@@ -1028,6 +1066,83 @@ def ttft_quantiles(problems: np.ndarray, rates, eps, device: Optional[str] = Non
     warn_if_pure_python_fallback()
     return _ttft_quantiles_python(
         problems, rates, eps, np.ones(n_rows) if scv_arr is None else scv_arr)
+
+
+def itl_quantiles(problems: np.ndarray, rates, eps, device: Optional[str] = None,
+                  large_n: Optional[bool] = None) -> np.ndarray:
+    """The ITL that a share ``eps`` of each row's tokens exceeds at the
+    per-replica rate ``rates`` (req/s): [B, 12] problems -> [B, 2] of ``(Q_VALID,
+    Q_ITL)`` (csrc/queue_core.h, "ITL quantile"; ``QueueAnalyzer.itl_quantile``
+    is the definition).  ``eps = 0.05`` asks for the p95 ITL in ms.
+
+    ``rates`` and ``eps`` follow ``_scv_vector``'s rules: a scalar for the whole
+    batch or a float64 ``[B]`` array.  There is no ``scv``: occupancy does not
+    depend on the wait scale.  A row gets ``(0, 0)`` when it breaks the row
+    contract, its ``eps`` is no finite number in the open (0, 1), or its rate is
+    NaN, infinite, <= 0 or above the rate range's maximum.
+
+    device: as in ``solve_problems``.  On ``cuda`` the rows with N <=
+    GPU_MAX_BATCH_LIMIT (invalid rows ride along) run on the ITL quantile
+    kernel, one ``submit_itl_quantile`` launch.  With ``large_n`` on, the rows up
+    to GPU_COMPACT_MAX_BATCH_LIMIT take a second launch of the same kernel,
+    which reserves LDS for them alone and is enqueued before anything is
+    collected.  Every other row runs on the native CPU solver while the
+    launches run.  Off the GPU: the torch-free binding, else the torch binding,
+    else the Python analyzer.
+
+    large_n: as in ``solve_problems``; ``None`` asks ``WVA_GPU_LARGE_N``.  No
+    effect off the GPU, on rows with N <= GPU_MAX_BATCH_LIMIT, or under
+    ``WVA_GPU_GRAPH=1``."""
+    from . import get_native, get_native_cpu, native_available, native_cpu_available
+
+    problems = np.ascontiguousarray(problems, dtype=np.float64)
+    if problems.ndim != 2 or problems.shape[1] != PROBLEM_FIELDS:
+        raise ValueError(f"problems must be [B, {PROBLEM_FIELDS}]")
+    n_rows = problems.shape[0]
+    rates = _scv_vector(rates, n_rows, "rates")
+    eps = _scv_vector(eps, n_rows, "eps")
+    if n_rows == 0:
+        return np.zeros((0, QUANTILE_FIELDS), dtype=np.float64)
+
+    if device is not None and str(device).startswith("cuda"):
+        native = get_native()  # raises loudly if missing on a GPU box
+        limits = _valid_batch_limits(problems)
+        small = limits <= GPU_MAX_BATCH_LIMIT
+        if small.all():
+            with _on_device(device):
+                return native.collect(native.submit_itl_quantile(
+                    problems, int(limits.max()), rates, eps))
+        middle = ~small & (limits <= GPU_COMPACT_MAX_BATCH_LIMIT)
+        if not _large_n_requested(large_n):
+            middle[:] = False
+        host = ~small & ~middle
+        out = np.empty((n_rows, QUANTILE_FIELDS), dtype=np.float64)
+        tickets = []
+        try:
+            for mask in (small, middle):
+                if mask.any():
+                    rows, row_rates, row_eps = _masked(mask, problems, rates, eps)
+                    with _on_device(device):
+                        tickets.append((mask, native.submit_itl_quantile(
+                            rows, int(limits[mask].max()), row_rates, row_eps)))
+            if host.any():
+                out[host] = itl_quantiles(*_masked(host, problems, rates, eps), device="cpu")
+        finally:  # a launch already enqueued must not keep its slot for good
+            for mask, ticket in tickets:
+                out[mask] = native.collect(ticket)
+        return out
+
+    if native_cpu_available():
+        return get_native_cpu().itl_quantiles(problems, rates, eps)
+    if native_available():
+        import torch
+
+        return get_native().itl_quantiles(
+            torch.from_numpy(problems), torch.from_numpy(rates), torch.from_numpy(eps)).numpy()
+    from . import warn_if_pure_python_fallback
+
+    warn_if_pure_python_fallback()
+    return _itl_quantiles_python(problems, rates, eps)
 
 
 def _resolved_scv(scv_rows, global_scv: float) -> np.ndarray:
@@ -1227,6 +1342,11 @@ class BatchedAllocationSolver:
     ``itl_percentile`` does the same for the ITL target (module docstring,
     "ITL percentile"); ``None`` asks ``WVA_ITL_PERCENTILE``.  On the GPU those
     rows run on the percentile kernel, which takes their TTFT percentile along.
+    Under either knob the feasible allocations also carry the prediction at
+    that percentile (``Allocation.ttft_percentile``, ``Allocation.itl_percentile``;
+    the latter for servers with an ITL target), from one ``ttft_quantiles`` and
+    one ``itl_quantiles`` call after the pipeline has drained, back to back.
+    With both knobs unset no row list is kept and neither call is made.
     """
 
     def __init__(self, device: Optional[str] = None, chunks: Optional[int] = None,
@@ -1289,6 +1409,23 @@ class BatchedAllocationSolver:
             if valid == 1.0:
                 alloc.ttft_percentile = q
 
+    def _predict_itl_percentiles(self, jobs, eps: float) -> None:
+        """``itl_percentile`` of every allocation in ``jobs`` whose row has an
+        ITL target (the rows the knob sized; ``create_allocation`` predicts for
+        the same ones): one ``itl_quantiles`` call at ``_predict_percentiles``'
+        rate and ``large_n``.  It runs after the TTFT prediction has been
+        collected, back to back: the two share the job list, not the stream."""
+        jobs = [job for job in jobs if job[1][P_TARGET_ITL] > 0]
+        if not jobs:
+            return
+        problems = np.array([row for _, row, _ in jobs], dtype=np.float64)
+        rates = problems[:, P_TOTAL_RATE] / np.array([a.num_replicas for a, _, _ in jobs],
+                                                     dtype=np.float64)
+        solved = itl_quantiles(problems, rates, eps, device=self.device, large_n=self.large_n)
+        for (alloc, _, _), (valid, q) in zip(jobs, solved.tolist()):
+            if valid == 1.0:
+                alloc.itl_percentile = q
+
     def calculate(self, system: System) -> None:
         for g in system.accelerators.values():
             g.calculate()
@@ -1335,8 +1472,10 @@ class BatchedAllocationSolver:
         servers = system.servers
         # percentile sizing: every feasible allocation also gets its predicted
         # TTFT at that percentile, from one ttft_quantiles call after the
-        # pipeline has drained: (allocation, row, its cs^2)
-        eps = dispatch.ttft_tail
+        # pipeline has drained, and under an ITL percentile its predicted ITL,
+        # from one itl_quantiles call behind it: (allocation, row, its cs^2)
+        eps, itl_eps = dispatch.ttft_tail, dispatch.itl_tail
+        keep_rows = eps > 0 or itl_eps > 0
         quantile_jobs: List[Tuple[Allocation, Tuple[float, ...], float]] = []
 
         def build_rows(chunk_servers):
@@ -1412,7 +1551,7 @@ class BatchedAllocationSolver:
             ticket = None
             if rows:
                 ticket = dispatch.submit(np.array(rows, dtype=np.float64), scv_rows)
-            return ticket, keys, zero_load, (rows, scv_rows) if eps > 0 else None
+            return ticket, keys, zero_load, (rows, scv_rows) if keep_rows else None
 
         def apply_results(ticket, keys, zero_load, submitted=None):
             """Collect one slice and turn its results into Allocations."""
@@ -1480,8 +1619,10 @@ class BatchedAllocationSolver:
             if pending is not None:
                 last, pending = pending, None
                 apply_results(*last)
-            if quantile_jobs:
+            if quantile_jobs and eps > 0:
                 self._predict_percentiles(quantile_jobs, eps, dispatch.global_scv)
+            if quantile_jobs and itl_eps > 0:
+                self._predict_itl_percentiles(quantile_jobs, itl_eps)
         finally:
             # an exception between submit and collect must not leave a
             # launch uncollected (its slot would stay busy for good)
