@@ -67,16 +67,23 @@ def _above(key, rate):
 
 
 def _case(n, frac, eps, **kw):
-    row = _row(n, **kw)
+    case = case_of(_row(n, **kw), frac, eps)
+    assert not case["tie"], (n, frac, eps)  # the honest-check condition; move the rate on a tie
+    del case["tie"]
+    return case
+
+
+def case_of(row, frac, eps):
+    """``_case`` on any valid row; ``tie``: eps within a relative 1e-6 of S_{b*-1} or S_{b*}."""
+    n = int(row[B.P_MAX_BATCH])
     rate = _top(row) * frac
     above = _above(tuple(row), rate)
     with localcontext() as ctx:
         ctx.prec = 50
         cut = D(eps) * above[0]
         b = next(b for b in range(1, n + 1) if above[b] <= cut)
-        for s in (above[b - 1], above[b]):  # the honest-check condition; move the rate on a tie
-            assert s == 0 or abs(cut / s - 1) > D("1e-6"), (n, frac, eps)
-    return {"row": row, "rate": rate, "eps": eps, "b": b}
+        tie = any(s != 0 and abs(cut / s - 1) <= D("1e-6") for s in (above[b - 1], above[b]))
+    return {"row": row, "rate": rate, "eps": eps, "b": b, "tie": tie}
 
 
 @lru_cache(maxsize=None)

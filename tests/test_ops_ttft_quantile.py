@@ -32,7 +32,10 @@ NAN, INF = float("nan"), float("inf")
 
 
 def _at(n, f):
-    row = _row(n)
+    return at_of(_row(n), f)
+
+
+def at_of(row, f):
     lam_min, lam_max = oracle.rate_range(row)
     lam = lam_min + D(f) * (lam_max - lam_min)
     return row, lam, oracle.evaluate(row, lam)
@@ -40,22 +43,34 @@ def _at(n, f):
 
 def _known(n, f, mult, scv=1.0):
     """The known-answer case of one cell, or None where it is dropped."""
-    row, lam, at = _at(n, f)
+    return known_of(_row(n), f, mult, scv)[0]
+
+
+def known_of(row, f, mult, scv=1.0):
+    """``_known`` on any valid row: (case, None), or (None, the reason it is
+    dropped)."""
+    row, lam, at = at_of(row, f)
     if at.wait < oracle.WAIT_FLOOR * at.serv:
-        return None
+        return None, "wait_floor"
     t = D(mult) * at.wait
     y, up, dn = (tail_oracle.exceedance(row, lam, t * s) for s in (1, 1 + _H, 1 - _H))
+    if not D("1e-280") < y < 1:
+        return None, "eps_out_of_range"
     slope = abs((up - dn) / (2 * _H) / y)  # |t y'(t) / y|
     if not slope or 1 / slope > 100:
-        return None
+        return None, "ill_conditioned"
     return {"row": row, "rate": float(lam * 1000), "eps": float(y), "scv": scv, "t": float(t),
-            "prefill": float(at.ttft - at.wait), "tol": 2e-6 * float(1 / slope) + 1e-9}
+            "prefill": float(at.ttft - at.wait), "tol": 2e-6 * float(1 / slope) + 1e-9}, None
 
 
 def _nobody_waits(n):
-    row, lam, at = _at(n, "0.5")
+    return nobody_waits_of(_row(n))
+
+
+def nobody_waits_of(row, f="0.5", scv=1.0):
+    row, lam, at = at_of(row, f)
     p_wait = tail_oracle.exceedance(row, lam, D("1e-30"))
-    return {"row": row, "rate": float(lam * 1000), "eps": float((1 + p_wait) / 2), "scv": 1.0,
+    return {"row": row, "rate": float(lam * 1000), "eps": float((1 + p_wait) / 2), "scv": scv,
             "t": 0.0, "prefill": float(at.ttft - at.wait), "tol": None}
 
 

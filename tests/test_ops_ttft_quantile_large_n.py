@@ -13,6 +13,7 @@ J - 1 and then the centre itself.  The ``*_small_n`` runs take
 ``test_ops_ttft_quantile``'s table, where J = 10 N is below the 64 chunks.
 """
 
+from decimal import Decimal as D
 from functools import lru_cache
 
 import numpy as np
@@ -20,6 +21,7 @@ import pytest
 
 import mm1k_oracle as oracle
 import test_ops_ttft_quantile as Q
+import ttft_tail_oracle as tail_oracle
 from fixtures import make_system, server_spec
 from test_ops_ttft_tail import BAD_EPS, FINAL_TOL, _row
 from wva_amd import ops
@@ -89,6 +91,78 @@ def test_oracle_table(impl, cases):
         worst = max(worst, abs(t_got / c["t"] - 1) / c["tol"])
         assert abs(t_got - c["t"]) <= c["t"] * c["tol"], (what, t_got, c["t"], c["tol"])
     print(f"{impl}: worst oracle error / bound = {worst:.3g}")
+
+
+# (N, fraction of the rate range, t in units of J / (20 mu_N)): eps of 1e-47 ...
+# 1e-202 at a moderate load, where u = exp((J - i) d) underflows and
+# quantile_sum_chunk leaves its chain for tail_sum_chunk's expm1 per term
+SMALL_EPS_CELLS = ((701, "0.9", "3"), (701, "0.8", "3"), (1024, "0.85", "0.5"), (7680, "0.97", "3"))
+CHAIN_MAX_EXPONENT, CHUNKS = 690.0, 64  # queue_core.h: kChainMaxExponent, kQuantileChunks
+
+
+def chunks_on_fallback(case):
+    """(chunks of the window at the case's t that take the expm1 fallback, the
+    non-empty chunks), from the window rule stated in queue_core.h
+    (tail_sweep_at) and the switch of quantile_sum_chunk."""
+    m = oracle.model_of(case["row"])
+    lam, mu_n, big_j = case["rate"] / 1000, float(m.mu[-1]), 10 * m.n
+    d = np.log(lam) - np.log(mu_n)
+    c = np.floor(min(lam * case["t"], big_j - 1))
+    span = 37.54 + 2 * np.log(big_j)
+    h = 2 * span + 1 + np.sqrt(2 * span * c)
+    lo, hi = int(max(c - h, 0)), int(min(c + h, big_j - 1))
+    length = (hi - lo + CHUNKS) // CHUNKS
+    starts = [lo + part * length for part in range(CHUNKS) if lo + part * length <= hi]
+    return sum((big_j - i0) * d < -CHAIN_MAX_EXPONENT for i0 in starts), len(starts)
+
+
+@lru_cache(maxsize=None)
+def small_eps_case(n, f, mult):
+    """The known answer at t = mult J / (20 mu_N): Q._known with t given in
+    service times, since the mean wait says nothing about a 1e-100 tail."""
+    row, lam, at = Q._at(n, f)
+    t = D(mult) * 10 * n / (20 * oracle.model_of(row).mu[-1])
+    y, up, dn = (tail_oracle.exceedance(row, lam, t * s) for s in (1, 1 + Q._H, 1 - Q._H))
+    cond = float(1 / abs((up - dn) / (2 * Q._H) / y))
+    assert D("1e-280") < y < D("1e-40") and cond <= 100, (n, f, mult, y, cond)
+    return {"row": row, "rate": float(lam * 1000), "eps": float(y), "scv": 1.0, "t": float(t),
+            "prefill": float(at.ttft - at.wait), "tol": 2e-6 * cond + 1e-9}
+
+
+@lru_cache(maxsize=None)
+def small_eps_table():
+    cases = [small_eps_case(*cell) for cell in SMALL_EPS_CELLS]
+    # a later change of the window must not take the cases off the path they are for
+    mixed, *rest = (chunks_on_fallback(c) for c in cases)
+    assert 0 < mixed[0] < mixed[1], mixed  # chunks on each side of kChainMaxExponent
+    assert all(fallback == chunks > 32 for fallback, chunks in rest), rest
+    return cases
+
+
+@pytest.mark.parametrize("impl", IMPL_PARAMS)
+def test_small_eps_takes_the_fallback_chunk(impl):
+    """The expm1 fallback of quantile_sum_chunk, alone and mixed with the
+    chain in one evaluation, holds the table's bound on t."""
+    _check_t(impl, IMPLS[impl], small_eps_table())
+
+
+@pytest.mark.parametrize("impl", [k if k in ("python", "cpu", "torch") else pytest.param(k, marks=gpu)
+                                  for k in Q.IMPLS])
+def test_small_eps_overlay(impl):
+    """The N <= 700 analogue (N = 700, 0.9 of the rate range, t = 3 J / (20
+    mu_N)) on the overlay quantile paths: no chain there, but no eps below 1e-3
+    in their own table either."""
+    _check_t(impl, Q.IMPLS[impl], [small_eps_case(700, "0.9", "3")])
+
+
+def _check_t(impl, solve, cases):
+    out = solve(*Q.arrays(cases))
+    for (valid, q), c in zip(out, cases):
+        t_got = (q - c["prefill"]) / ((1 + c["scv"]) / 2)
+        what = (int(c["row"][B.P_MAX_BATCH]), c["rate"], c["eps"], t_got, c["t"], c["tol"])
+        print(f"{impl}: N = {what[0]}, eps = {c['eps']:.3g}: error / bound = "
+              f"{abs(t_got / c['t'] - 1) / c['tol']:.3g}")
+        assert valid == 1.0 and abs(t_got - c["t"]) <= c["t"] * c["tol"], what
 
 
 @pytest.mark.parametrize("impl", IMPL_PARAMS)

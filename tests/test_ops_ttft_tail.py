@@ -55,12 +55,18 @@ def _case(row, eps, lam, rate_tol, scv=1.0):
 
 def _known(n, f, mult, scv=1.0):
     """The known-answer case of one cell, or None where it is dropped."""
-    row, ws = _row(n), (D(1) + D(scv)) / 2
+    return known_of(_row(n), f, mult, scv)[0]
+
+
+def known_of(row, f, mult, scv=1.0):
+    """``_known`` on any valid row with no targets set (the row is written
+    to): (case, None), or (None, the reason it is dropped)."""
+    ws = (D(1) + D(scv)) / 2
     lam_min, lam_max = oracle.rate_range(row)
     lam = lam_min + D(f) * (lam_max - lam_min)
     at = oracle.evaluate(row, lam)
     if at.wait < oracle.WAIT_FLOOR * at.serv:
-        return None
+        return None, "wait_floor"
     row[B.P_TARGET_TTFT] = float(ws * D(mult) * at.wait + at.ttft - at.wait)
 
     def y(rate):
@@ -70,7 +76,38 @@ def _known(n, f, mult, scv=1.0):
     slope_y = abs((y(up) - y(dn)) / y(lam))
     slope_thr = abs(oracle.evaluate(row, up).throughput - oracle.evaluate(row, dn).throughput)
     cond = float(slope_thr / at.throughput / slope_y) if slope_y else float("inf")
-    return _case(row, y(lam), lam, 2e-6 * cond + 1e-9, scv) if cond <= 100 else None
+    if cond > 100:
+        return None, "ill_conditioned"
+    eps = y(lam)
+    if not D("1e-280") < eps < 1:
+        return None, "eps_out_of_range"
+    return _case(row, eps, lam, 2e-6 * cond + 1e-9, scv), None
+
+
+def _with_target(row, target_ttft):
+    row = row.copy()
+    row[B.P_TARGET_TTFT] = target_ttft
+    return row
+
+
+def no_search_of(row):
+    """The cases of ``row`` (no targets set) that no search decides: lam* at the
+    cap, and the one or two infeasible ones."""
+    lam_min, lam_max = oracle.rate_range(row)
+    top, bottom = oracle.evaluate(row, lam_max), oracle.evaluate(row, lam_min)
+    # eps above y(lam_max): lam* = lam_max
+    above = _with_target(row, float(2 * top.ttft))
+    y_top = tail_oracle.ttft_exceedance(above, lam_max, above[B.P_TARGET_TTFT])
+    cases = [_case(above, (1 + y_top) / 2, lam_max, FINAL_TOL)]
+    # target_ttft <= prefill at every rate: P = 1 > eps (a decode-only row has no prefill)
+    if bottom.ttft > bottom.wait:
+        cases.append(_case(_with_target(row, float((bottom.ttft - bottom.wait) / 2)), 0.05, None, None))
+    # eps below y(lam_min), where that is a float at all
+    below = _with_target(row, float(bottom.ttft - bottom.wait + 1 / oracle.model_of(row).mu[-1]))
+    y_bottom = tail_oracle.ttft_exceedance(below, lam_min, below[B.P_TARGET_TTFT])
+    if y_bottom > D("1e-280"):
+        cases.append(_case(below, y_bottom / 2, None, None))
+    return cases
 
 
 @lru_cache(maxsize=None)
@@ -82,20 +119,7 @@ def table():
     assert {int(c["row"][B.P_MAX_BATCH]) for c in cases} == set(BATCH_LIMITS), "an N lost"
     cases.append(_known(64, "0.9", "3", scv=0.25))
     for n in BATCH_LIMITS:
-        row = _row(n)
-        lam_min, lam_max = oracle.rate_range(row)
-        top, bottom = oracle.evaluate(row, lam_max), oracle.evaluate(row, lam_min)
-        # eps above y(lam_max): lam* = lam_max
-        above = _row(n, float(2 * top.ttft))
-        y_top = tail_oracle.ttft_exceedance(above, lam_max, above[B.P_TARGET_TTFT])
-        cases.append(_case(above, (1 + y_top) / 2, lam_max, FINAL_TOL))
-        # target_ttft <= prefill at every rate: P = 1 > eps
-        cases.append(_case(_row(n, float((bottom.ttft - bottom.wait) / 2)), 0.05, None, None))
-        # eps below y(lam_min), where that is a float at all
-        below = _row(n, float(bottom.ttft - bottom.wait + 1 / oracle.model_of(row).mu[-1]))
-        y_bottom = tail_oracle.ttft_exceedance(below, lam_min, below[B.P_TARGET_TTFT])
-        if y_bottom > D("1e-280"):
-            cases.append(_case(below, y_bottom / 2, None, None))
+        cases += no_search_of(_row(n))
     assert sum(c["lam"] is None for c in cases) > len(BATCH_LIMITS)
     return cases
 
